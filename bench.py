@@ -9,7 +9,14 @@ same matrix is solved by all ranks together (strong scaling), with an RCCL
 all-reduce of the K x K Gramian and an in-place all-gather of the solved factor
 shards every half-epoch.
 
-Objects on the line:
+A plain run sets up, warms up, times the steps and prints the headline (``value``, ``ms_per_step``;
+for N > 1 also which path was timed).  ``--dump-outputs DIR`` writes the factors the last timed step
+left, ``DIR/user.npy`` and ``DIR/item.npy`` (float32; above 63 MB, a seeded sample of their rows).
+``--full`` adds everything else below: it times the dominant kernel with HIP events inside the timed
+steps, runs two untimed profiling epochs, the ceilings, the secondary legs and the CPU baseline, and
+for N > 1 the per-phase split and the sharded legs.
+
+Objects on the --full line:
   roofline      dominant kernel of the headline (Cholesky) run, HIP-event timed inside the
                 library on the launch stream; both the flop side and the HBM side
   ceilings      copy / triad GB/s, pure fp32-MFMA TF and LDS-atomic rate MEASURED in this run,
@@ -50,6 +57,11 @@ def parse_args():
     ap.add_argument("--shape", default="ml20m")
     ap.add_argument("--K", type=int, default=64)
     ap.add_argument("--solver", default="CHOLESKY", choices=["CHOLESKY", "CG"])
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline: per-kernel times and rooflines, ceilings, "
+                         "secondary legs, the CPU baseline, the N > 1 per-phase split")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the factors of the last timed step to DIR/user.npy and DIR/item.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-secondary", action="store_true",
@@ -972,6 +984,23 @@ def _exchange_ab(trainer, local, sc, barrier) -> dict:
     return out
 
 
+DUMP_LIMIT_BYTES = 63 * 10 ** 6  # (--dump-outputs stays under 64 MB with the .npy headers)
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes each array as ``out_dir/<name>.npy``.  When together they exceed DUMP_LIMIT_BYTES, every
+    array keeps the same fraction of its rows, chosen by a fixed seed and kept in row order, so that two
+    builds run with the same arguments write the same rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    keep = min(1.0, DUMP_LIMIT_BYTES / max(total, 1))
+    rng = np.random.default_rng(0)
+    for name, a in arrays.items():
+        if keep < 1.0:
+            a = a[np.sort(rng.choice(a.shape[0], int(a.shape[0] * keep), replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def launch_ranks(args, argv):
     """``python bench.py --gpus N`` (N > 1) WITHOUT an outer torch.distributed.run: start the N ranks as a
     CHILD process - the launcher the driver itself uses - before this process has touched the GPU (no HIP
@@ -1095,7 +1124,7 @@ def main():
             preflight["error"] = trainer.native_error
         preflight["peers_mapped"] = bool(getattr(local, "peers_attached", False))
     native = bool(trainer.native)
-    if multi and not native:  # the host loop is the timed path: it carries the phase marks itself
+    if multi and not native and args.full:  # the host loop is the timed path: it carries the phase marks itself
         trainer.timing = True
 
     def barrier():
@@ -1117,11 +1146,12 @@ def main():
         trainer.step(sc)
     trainer.synchronize()
     trainer.last_timing()  # drop the warm-up marks
-    # The timed steps carry HIP events on the dominant kernel only (the solve of the side with more
-    # rows) - the roofline below is priced on its duration, measured live in this region; event pairs
-    # on all ten launches of an epoch cost 0.05 ms of 2.1.  The other kernels' durations come from two
-    # extra, untimed epochs afterwards.
-    local.trainer.profile(2)
+    # With --full the timed steps carry HIP events on the dominant kernel only (the solve of the side
+    # with more rows) - the roofline below is priced on its duration, measured live in this region;
+    # event pairs on all ten launches of an epoch cost 0.05 ms of 2.1.  The other kernels' durations
+    # come from two extra, untimed epochs afterwards.
+    if args.full:
+        local.trainer.profile(2)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -1129,19 +1159,28 @@ def main():
     trainer.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
-    prof = local.trainer.profile_read()
-    local.trainer.profile(True)
-    for _ in range(2):
-        trainer.step(sc)
-    trainer.synchronize()
-    for name, rec in local.trainer.profile_read().items():
-        prof.setdefault(name, rec)  # (the dominant kernel keeps its timed-region figure)
-    local.trainer.profile(False)
+    if args.dump_outputs and rank == 0:  # (the factors are replicated on every rank)
+        dump_outputs(args.dump_outputs, {"user": local.trainer.user, "item": local.trainer.item})
+    prof = {}
+    if args.full:
+        prof = local.trainer.profile_read()
+        local.trainer.profile(True)
+        for _ in range(2):
+            trainer.step(sc)
+        trainer.synchronize()
+        for name, rec in local.trainer.profile_read().items():
+            prof.setdefault(name, rec)  # (the dominant kernel keeps its timed-region figure)
+        local.trainer.profile(False)
     comm = None
     if multi:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+        comm = {"timed_path": ((f"native: irs_ials_sharded_step (transport {trainer.native_transport} inside the "
+                                f"library, row exchange '{trainer.native_exchange}', in-place rows, next Gramian "
+                                "overlapped)") if native else "torch.distributed host loop"),
+                "native_preflight": preflight, "exchange_ab": exchange_ab}
+    if multi and args.full:
         # per-phase device time of the timed epochs (events on the stream the kernels and the
         # collectives' waits run on), per step; max and min over ranks
         phase_steps = args.steps
@@ -1168,11 +1207,7 @@ def main():
                 "per_step_ms_min_over_ranks": {k: float(v) for k, v in zip(keys, lo.tolist())},
                 "compute_ms": float(hi[0] + hi[2]), "allreduce_ms": float(hi[1]),
                 "allgather_ms": float(hi[3]), "exposed_comm_ms": float(hi[4]),
-                "exchange": exchange_plan, "overlap": bool(trainer.overlap),
-                "timed_path": ((f"native: irs_ials_sharded_step (transport {trainer.native_transport} inside the "
-                                f"library, row exchange '{trainer.native_exchange}', in-place rows, next Gramian "
-                                "overlapped)") if native else "torch.distributed host loop"),
-                "native_preflight": preflight, "exchange_ab": exchange_ab,
+                "exchange": exchange_plan, "overlap": bool(trainer.overlap), **comm,
                 "phase_split_from": "torch.distributed host loop" + (" (extra untimed epochs)" if native else ""),
                 "note": "solve_ms spread (max - min over ranks) = load imbalance; the collectives' "
                         "time includes waiting for the slowest rank"}
@@ -1181,7 +1216,7 @@ def main():
     # Every rank takes part; a failing leg (the same exception on every rank: arguments, memory) is
     # recorded instead of costing the headline line.
     sharded_sec = {}
-    if multi and not args.no_secondary and K <= 64:
+    if multi and args.full and not args.no_secondary and K <= 64:
         legs_n = [s for s in args.legs.split(",") if s]
         for name, fn in (("knn", lambda: knn_sharded_leg(X, local_rank, barrier)),
                          ("evaluator", lambda: evaluator_sharded_leg(X, K, local_rank, barrier))):
@@ -1195,7 +1230,7 @@ def main():
             sharded_sec[name]["leg_wall_s"] = time.perf_counter() - t0
 
     result = None
-    if rank == 0:
+    if rank == 0 and args.full:
         ceilings = None
         try:
             ceilings = _lib.measure_ceilings(local_rank)
@@ -1213,7 +1248,6 @@ def main():
                        "out of a 1 GiB table; best of 3-5, HIP events"})
         except Exception as exc:  # the headline line must still be printed
             ceilings = {"error": repr(exc)}
-        value = (U + I) * args.steps / elapsed
         # dominant kernel of this rank and its roofline
         dom = max(prof.items(), key=lambda kv: kv[1]["ms"]) if prof else (None, None)
         roofline = None
@@ -1257,6 +1291,8 @@ def main():
             roofline["traffic"] = pmc.get(name)
             roofline["traffic_provenance"] = pmc.get("_provenance") or pmc.get("_stale") or (
                 "no PMC pass of this workload is committed" if world == 1 else "N > 1: per-rank shards, no pass")
+    if rank == 0:
+        value = (U + I) * args.steps / elapsed
         result = {
             "metric": "iALS user+item updates/sec at k=64, ML-20M-shape CSR",
             "value": value,
@@ -1279,11 +1315,11 @@ def main():
                 "balance": balance,
             },
             "comm": comm,
-            "kernels_ms_per_launch": {k: round(v["ms"] / v["launches"], 4) for k, v in prof.items()},
-            "roofline": roofline,
-            "ceilings": ceilings,
         }
-        if world == 1 and not args.no_secondary:
+        if args.full:
+            result.update({"kernels_ms_per_launch": {k: round(v["ms"] / v["launches"], 4) for k, v in prof.items()},
+                           "roofline": roofline, "ceilings": ceilings})
+        if world == 1 and args.full and not args.no_secondary:
             legs = [s for s in args.legs.split(",") if s]
             sec = {}
 
@@ -1318,7 +1354,7 @@ def main():
         if sharded_sec:
             result["secondary"] = sharded_sec
         # last: 256 busy host threads just before a GPU leg disturb its (host-clocked) timing
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(X, K, args.solver, args.cpu_seconds)
     if multi:
         dist.barrier()

@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out/prof
 cd $R
-ARGS="--legs c4 --no-cpu-baseline"
+ARGS="--full --legs c4 --no-cpu-baseline"
 [ "$FULL" = "1" ] || ARGS="$ARGS --c4-small"
 rm -rf gpurun_out/prof/c4_sq gpurun_out/prof/c4_sq2 gpurun_out/prof/c4_hbm
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE --output-format csv -d gpurun_out/prof/c4_sq -- python3 bench.py $ARGS > gpurun_out/prof/c4_sq.log 2>&1

@@ -12,7 +12,8 @@ rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/prof/sec_fetch -- p
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/prof/sec_write -- python3 scripts/quick_knn_eval.py --skip-eval > gpurun_out/prof/sec_write.log 2>&1
 # short-row kernels (C4 shape at 1/5 scale, K = 128, CG and Cholesky)
 rm -rf gpurun_out/prof/c4_kt
-rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof/c4_kt -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --legs c4 --c4-small > gpurun_out/prof/c4_kt.log 2>&1
+P=$(python3 -c 'import sys; sys.path.insert(0, "scripts"); import summarize_prof; print(summarize_prof.SRC)')  # where summarize_prof.py reads the passes
+rocprofv3 --kernel-trace --stats --output-format csv -d "$P/c4_kt" -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --legs c4 --c4-small > "$P/c4_kt.log" 2>&1
 ls gpurun_out/prof | head -40
 # fused iALS evaluator (quick_eval_fused.py: 4 calls over all users at K = 64 and K = 256)
 bash scripts/prof_eval_fused.sh > gpurun_out/prof/ef.log 2>&1

@@ -131,7 +131,7 @@ def test_bench_two_ranks_control_flow(extra, env_extra, timed):
         launcher = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                     "--master-addr", "127.0.0.1", "--master-port", str(_free_port())]
     out = subprocess.run(
-        [*launcher, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", *extra],
+        [*launcher, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", *extra],
         env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -176,7 +176,7 @@ def test_bench_rccl_path_with_one_rank():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                          "--shape", "small", "--balance", "equal", "--no-secondary", "--no-cpu-baseline"],
+                          "--full", "--shape", "small", "--balance", "equal", "--no-secondary", "--no-cpu-baseline"],
                          env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
