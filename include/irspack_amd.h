@@ -64,9 +64,9 @@ typedef struct irs_ials_model_config {
   float init_stdev;
   int32_t random_seed;
   int32_t loss_type;
-  float lambda_user_feature;  /* feature-aware iALS: used by the host-side ridge update of */
-  float lambda_item_feature;  /* the feature weights (see irs_ials_set_prior); carried    */
-  uint64_t feature_warmup_epochs; /* here for the pickle state.                            */
+  float lambda_user_feature;  /* feature-aware iALS: the ridge terms of the feature-weight  */
+  float lambda_item_feature;  /* updates and the plain epochs before the first feature one */
+  uint64_t feature_warmup_epochs; /* (irs_ials_feature_step).                              */
 } irs_ials_model_config;
 
 /* SolverConfig, IALSLearningConfig.hpp:97-112 (als/wrapper.cpp:92-115) */
@@ -103,7 +103,9 @@ irs_status irs_ials_create_from_factors(const irs_ials_model_config *config,
                                         int32_t device, irs_ials_trainer **out);
 irs_status irs_ials_destroy(irs_ials_trainer *t);
 
-/* IALSTrainer::step, hpp:758-789: P_u, user solve, P_i, item solve. */
+/* IALSTrainer::step, hpp:784-788: P_u, user solve, P_i, item solve - the plain epoch, also on a
+ * trainer with features (irs_ials_feature_step runs the feature-aware one).  Advances the epoch
+ * counter that irs_ials_feature_step's warm-up reads. */
 irs_status irs_ials_step(irs_ials_trainer *t, const irs_ials_solver_config *sc);
 /* `.user` / `.item` read-write attributes, als/wrapper.cpp:158-159.
  * which: 0 = user, 1 = item.  out/in are C-contiguous float32 [rows, K]. */
@@ -130,10 +132,11 @@ irs_status irs_ials_transform_with_prior(irs_ials_trainer *t, int32_t side, int6
                                          const int32_t *indices, const float *data,
                                          const float *prior,
                                          const irs_ials_solver_config *sc, float *out);
-/* Feature-aware training (IALSTrainer::step, hpp:758-789): the prior of side `which`
- * (host float32 [rows, K] = features @ feature_weight) used by the following
- * irs_ials_half_step_async calls of that side; NULL clears it.  The feature-weight ridge
- * update (hpp:1052-1209) is a small F x F host solve and stays with the caller. */
+/* Feature-aware training, piece by piece: the prior of side `which` (host float32 [rows, K] =
+ * features @ feature_weight) used by the following irs_ials_half_step_async calls of that side;
+ * NULL clears it.  irs_ials_feature_step runs the whole feature-aware epoch, ridge update of the
+ * feature weights (hpp:1052-1209) included, on the device; these calls remain for callers that
+ * drive the half steps themselves. */
 irs_status irs_ials_set_prior(irs_ials_trainer *t, int32_t which, const float *prior);
 /* The two feature products of feature-aware training on the device, so that the factor
  * matrices never leave HBM during an epoch.  irs_ials_set_features stores the feature
@@ -149,6 +152,24 @@ irs_status irs_ials_set_features(irs_ials_trainer *t, int32_t which, int64_t row
 irs_status irs_ials_apply_feature_prior(irs_ials_trainer *t, int32_t which,
                                         const float *weight);
 irs_status irs_ials_feature_rhs(irs_ials_trainer *t, int32_t which, float *out);
+/* IALSTrainer::step for a feature-aware trainer, hpp:758-789, in one call.  The epoch counter,
+ * warm-up (feature_warmup_epochs plain epochs first), IALSPP rejection, empty-row check
+ * (hpp:639-653), per-side prior -> solve -> ridge update of the feature weights, and the ridge
+ * LLT cache all live in the library.  A side without features (or with n_feat == 0) runs its
+ * plain half step.  The feature weights start at zero; the ridge system F^T D F + lambda I is
+ * formed and factorised on the device once per side and kept until irs_ials_set_features
+ * replaces that side's features.  One synchronisation, at the end.  Errors: IALSPP and an
+ * undefined empty-row prior are invalid arguments; "Feature ridge Cholesky decomposition
+ * failed." / "Feature ridge solve failed." are runtime errors (hpp:1104-1105, 1169-1170), after
+ * which the weights keep their previous values.  Not available on a sharded trainer. */
+irs_status irs_ials_feature_step(irs_ials_trainer *t, const irs_ials_solver_config *sc);
+/* The `.user_feature_weight` / `.item_feature_weight` attributes (als/wrapper.cpp:160-161):
+ * float32 [n_feat, K], C-contiguous, resident on the device.  get writes nothing when the side
+ * has no weights.  set replaces W only (the cached ridge LLT stays); with features set, rows must
+ * be that side's n_feat; cols must be K. */
+irs_status irs_ials_get_feature_weight(irs_ials_trainer *t, int32_t which, float *out);
+irs_status irs_ials_set_feature_weight(irs_ials_trainer *t, int32_t which,
+                                       const float *in, int64_t rows, int64_t cols);
 /* IALSTrainer::compute_loss, hpp:836-940. */
 irs_status irs_ials_compute_loss(irs_ials_trainer *t,
                                  const irs_ials_solver_config *sc, float *out);

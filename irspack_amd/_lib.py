@@ -110,6 +110,9 @@ EXPORTED_SYMBOLS = [
     "irs_ials_set_features",
     "irs_ials_apply_feature_prior",
     "irs_ials_feature_rhs",
+    "irs_ials_feature_step",
+    "irs_ials_get_feature_weight",
+    "irs_ials_set_feature_weight",
     "irs_ials_compute_loss",
     "irs_ials_set_stream",
     "irs_ials_device_buffer",
@@ -154,6 +157,13 @@ EXPORTED_SYMBOLS = [
     "irs_measure_ceilings",
 ]
 
+# argument types of the feature-aware step and its weight accessors (irs_status return)
+ARGTYPES = {
+    "irs_ials_feature_step": [C.c_void_p, C.c_void_p],
+    "irs_ials_get_feature_weight": [C.c_void_p, C.c_int32, C.POINTER(C.c_float)],
+    "irs_ials_set_feature_weight": [C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_int64, C.c_int64],
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -170,6 +180,9 @@ def lib() -> C.CDLL:
         _lib.irs_last_error.restype = C.c_char_p
         _lib.irs_abi_version.restype = C.c_int32
         _lib.irs_device_count.restype = C.c_int32
+        for name, args in ARGTYPES.items():
+            getattr(_lib, name).argtypes = args
+            getattr(_lib, name).restype = C.c_int32
         if _lib.irs_abi_version() != ABI_VERSION:
             found = _lib.irs_abi_version()
             _lib = None

@@ -26,6 +26,7 @@
 #include "ials_wg16_kernels.hpp"
 #include "ials_pp_kernels.hpp"
 #include "ials_feature_kernels.hpp"
+#include "ials_ridge_kernels.hpp"
 #include "ials_short_kernels.hpp"
 #include "ials_gk_kernels.hpp"
 #include "ials_eig_kernels.hpp"
@@ -94,6 +95,7 @@ struct Side {
   bool unit = false;  // every stored confidence is exactly 1 (UNIT kernels)
   bool positive = false;  // every stored confidence is > 0 (eigenbasis short-row kernels)
   float reg_min = 0.f;    // smallest per-row regulariser of the rows [row_begin, row_end)
+  bool has_empty = false; // some row stores no entry (feature-aware step, hpp:639-653)
   bool entries_ready = false, indptr_ready = false;  // the device arrays were filled ahead of build()
 
   // The gather pipeline loads whole 64-entry blocks up to two blocks past a row's end: 320 zero entries
@@ -159,6 +161,8 @@ struct Side {
     });
     reg_min = 0.f;
     for (int64_t r = rb; r < re; r++) reg_min = r == rb ? regs[r] : std::min(reg_min, regs[r]);
+    has_empty = false;
+    for (int64_t r = 0; r < m.rows && !has_empty; r++) has_empty = m.indptr[r + 1] == m.indptr[r];
     const int CH = chunk_size();
     // (read per build, not once per process: the tests lower it to fold rows of 10^4 entries)
     const char *long_env = std::getenv("IRSPACK_AMD_IALS_CHUNK_LONG");
@@ -394,6 +398,12 @@ struct irs_ials_trainer {
   DeviceBuffer<int32_t> f_indptr[2], f_indices[2], ft_indptr[2], ft_indices[2];
   DeviceBuffer<float> f_data[2], ft_data[2], f_W[2], f_rhs[2], f_part[2];
   int f_chunks[2] = {1, 1};  // feature_rhs_kernel: chunks of FEATURE_RHS_CHUNK stored rows per feature
+  // irs_ials_feature_step (ials_ridge_kernels.hpp): per side the padded ridge system G -> L (kept
+  // until irs_ials_set_features replaces the features) and the [FP, KP] right-hand side / solution
+  int64_t w_rows[2] = {0, 0};  // rows of the feature weights in f_W (n_feat, or a restored pickle's)
+  DeviceBuffer<float> f_L[2], f_sol[2], f_gpart;
+  bool ridge_ready[2] = {false, false};
+  int64_t epoch = 0;  // IALSTrainer::epoch_ (hpp:762, 781, 788): both step calls advance it
   DeviceBuffer<float> pp_pred;         // iALS++ prediction cache (CSR-indexed, padded)
   DeviceBuffer<int32_t> pp_llt_sink;   // iALS++ does not test the LLT status (hpp:495-497)
   DeviceBuffer<float> pp_pblk;         // iALS++ chain path: blocks of P in accumulator layout
@@ -1607,6 +1617,9 @@ void sync_and_check(irs_ials_trainer *t) {
     IRS_HIP(hipStreamSynchronize(t->stream));
     if (flag & 1) throw std::runtime_error("Cholesky decomposition failed.");  // hpp:318
     if (flag & 2) throw std::runtime_error("Cholesky solve failed.");          // hpp:322
+    if (flag & RIDGE_FLAG_CHOL)  // hpp:1104-1105
+      throw std::runtime_error("Feature ridge Cholesky decomposition failed.");
+    if (flag & RIDGE_FLAG_SOLVE) throw std::runtime_error("Feature ridge solve failed.");  // hpp:1169-1170
     if (flag & 8)  // comm.hip: a peer's rows or Gramian did not arrive (IRSPACK_AMD_PEER_TIMEOUT_S)
       throw std::runtime_error("The sharded step timed out waiting for a peer's stores.");
     throw std::runtime_error(
@@ -2018,6 +2031,14 @@ irs_status irs_ials_synchronize(irs_ials_trainer *t) {
   });
 }
 
+// IALSTrainer::step, hpp:784-788 (launches only)
+static void plain_epoch(irs_ials_trainer *t, const irs_ials_solver_config *sc) {
+  full_gramian(t, 0);
+  launch_solve(t, t->side[0], t->factor[1].ptr, t->factor[0].ptr, 0, sc);
+  full_gramian(t, 1);
+  launch_solve(t, t->side[1], t->factor[0].ptr, t->factor[1].ptr, 1, sc);
+}
+
 // IALSTrainer::step, hpp:784-788
 irs_status irs_ials_step(irs_ials_trainer *t, const irs_ials_solver_config *sc) {
   return guard([&] {
@@ -2029,11 +2050,9 @@ irs_status irs_ials_step(irs_ials_trainer *t, const irs_ials_solver_config *sc) 
                   t->shard.item_begin == 0 && t->shard.item_end == t->n_items,
               "irs_ials_step needs an unsharded trainer; sharded runs drive the half "
               "steps from the host loop.");
-    full_gramian(t, 0);
-    launch_solve(t, t->side[0], t->factor[1].ptr, t->factor[0].ptr, 0, sc);
-    full_gramian(t, 1);
-    launch_solve(t, t->side[1], t->factor[0].ptr, t->factor[1].ptr, 1, sc);
+    plain_epoch(t, sc);
     sync_and_check(t);
+    t->epoch++;
   });
 }
 
@@ -2345,6 +2364,122 @@ irs_status irs_ials_set_prior(irs_ials_trainer *t, int32_t which, const float *p
 
 constexpr int64_t FEATURE_RHS_CHUNK = 2048;
 
+namespace {
+
+// prior[which] = features @ f_W  (feature_times_weight, hpp:702-708)
+void launch_feature_prior(irs_ials_trainer *t, int which) {
+  const int64_t n = t->rows_of(which);
+  t->prior[which].alloc(static_cast<size_t>(ceil_div(n, 8) * 8) * t->KP);
+  t->prof.begin(which == 0 ? "feature_prior_user" : "feature_prior_item", t->stream);
+  hipLaunchKernelGGL(feature_prior_kernel, dim3(ceil_div(n, 4), ceil_div(t->KP, 256)), dim3(256), 0, t->stream,
+                     t->f_indptr[which].ptr, t->f_indices[which].ptr, t->f_data[which].ptr,
+                     t->f_W[which].ptr, n, t->KP, t->prior[which].ptr);
+  t->prof.end(t->stream);
+  IRS_HIP(hipGetLastError());
+}
+
+// dst[:F] = features^T (reg_r factor_r)  (solve_feature_weight, hpp:1141-1167), [F, KP]
+void launch_feature_rhs(irs_ials_trainer *t, int which, float *dst) {
+  const int64_t F = t->n_feat[which];
+  t->prof.begin(which == 0 ? "feature_rhs_user" : "feature_rhs_item", t->stream);
+  const int nc = t->f_chunks[which];
+  hipLaunchKernelGGL(feature_rhs_kernel, dim3(F, nc, ceil_div(t->KP, 256)), dim3(256), 0, t->stream,
+                     t->ft_indptr[which].ptr, t->ft_indices[which].ptr, t->ft_data[which].ptr,
+                     t->side[which].reg.ptr, t->factor[which].ptr, t->KP,
+                     static_cast<int>(FEATURE_RHS_CHUNK), static_cast<int>(F),
+                     t->f_part[which].ptr);
+  hipLaunchKernelGGL(feature_rhs_reduce_kernel, dim3(ceil_div(F * t->KP, 256)), dim3(256), 0,
+                     t->stream, t->f_part[which].ptr, nc, F * t->KP, dst);
+  t->prof.end(t->stream);
+  IRS_HIP(hipGetLastError());
+}
+
+int64_t ridge_padded(int64_t F) { return ceil_div(F, RIDGE_NB) * RIDGE_NB; }
+
+// initialize_feature_weight_cache (hpp:1082-1130): G = F^T D F + lambda I and its LLT, kept in
+// f_L[which].  A failed pivot raises RIDGE_FLAG_CHOL; the caller marks the cache ready only after
+// the call's synchronisation found the flag clear.
+void launch_ridge_factorize(irs_ials_trainer *t, int which) {
+  const int64_t F = t->n_feat[which], FP = ridge_padded(F), nb = FP / RIDGE_NB;
+  const int64_t n_rows = t->rows_of(which);
+  const float lam = which == 0 ? t->cfg.lambda_user_feature : t->cfg.lambda_item_feature;
+  const int64_t n_tiles = nb * (nb + 1) / 2;
+  check_arg(n_tiles < (int64_t{1} << 31), "irspack_amd: too many feature columns for the ridge system.");
+  t->f_L[which].alloc(static_cast<size_t>(FP) * FP);
+  // slabs of rows (summed in order) only where the tiles alone leave the device idle
+  int64_t n_slabs = std::min<int64_t>({64, ceil_div(2048, n_tiles), std::max<int64_t>(1, ceil_div(n_rows, 256))});
+  n_slabs = std::max<int64_t>(n_slabs, 1);
+  const int64_t per = ceil_div(ceil_div(std::max<int64_t>(n_rows, 1), n_slabs), 16) * 16;
+  if (n_slabs > 1) t->f_gpart.alloc(static_cast<size_t>(n_slabs * n_tiles) * RIDGE_NB * RIDGE_NB);
+  hipStream_t s = t->stream;
+  t->prof.begin(which == 0 ? "feature_ridge_llt_user" : "feature_ridge_llt_item", s);
+  hipLaunchKernelGGL(ridge_gram_kernel, dim3(n_tiles, n_slabs), dim3(256), 0, s, t->f_indptr[which].ptr,
+                     t->f_indices[which].ptr, t->f_data[which].ptr, t->side[which].reg.ptr, n_rows, per,
+                     static_cast<int>(n_slabs), static_cast<int>(F), static_cast<int>(FP), lam,
+                     t->f_gpart.ptr, t->f_L[which].ptr);
+  if (n_slabs > 1) {
+    const int64_t n = n_tiles * RIDGE_NB * RIDGE_NB;
+    hipLaunchKernelGGL(ridge_gram_reduce_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, t->f_gpart.ptr,
+                       static_cast<int>(n_tiles), static_cast<int>(n_slabs), static_cast<int>(F),
+                       static_cast<int>(FP), lam, t->f_L[which].ptr);
+  }
+  float *L = t->f_L[which].ptr;
+  for (int64_t k = 0; k < nb; k++) {
+    hipLaunchKernelGGL(ridge_chol_diag_kernel, dim3(1), dim3(256), 0, s, L, static_cast<int>(FP),
+                       static_cast<int>(k), t->err_flag.ptr);
+    const int64_t below = FP - (k + 1) * RIDGE_NB, m = nb - k - 1;
+    if (below <= 0) continue;
+    hipLaunchKernelGGL(ridge_chol_trsm_kernel, dim3(ceil_div(below, 256)), dim3(256), 0, s, L,
+                       static_cast<int>(FP), static_cast<int>(k));
+    hipLaunchKernelGGL(ridge_chol_update_kernel, dim3(m * (m + 1) / 2), dim3(256), 0, s, L,
+                       static_cast<int>(FP), static_cast<int>(k));
+  }
+  t->prof.end(s);
+  IRS_HIP(hipGetLastError());
+}
+
+// solve_feature_weight (hpp:1132-1177): L L^T W = F^T (D factor) on the device, W into f_W
+void launch_ridge_solve(irs_ials_trainer *t, int which) {
+  const int64_t F = t->n_feat[which], FP = ridge_padded(F), nb = FP / RIDGE_NB;
+  const int KP = t->KP, ncb = static_cast<int>(ceil_div(KP, RIDGE_NB));
+  hipStream_t s = t->stream;
+  t->f_sol[which].alloc(static_cast<size_t>(FP) * KP);
+  if (FP > F)
+    IRS_HIP(hipMemsetAsync(t->f_sol[which].ptr + F * KP, 0, static_cast<size_t>(FP - F) * KP * sizeof(float), s));
+  launch_feature_rhs(t, which, t->f_sol[which].ptr);
+  const float *L = t->f_L[which].ptr;
+  float *S = t->f_sol[which].ptr;
+  t->prof.begin(which == 0 ? "feature_ridge_solve_user" : "feature_ridge_solve_item", s);
+  for (int64_t k = 0; k < nb; k++) {  // L Y = rhs
+    hipLaunchKernelGGL(ridge_trsv_fwd_diag_kernel, dim3(ncb), dim3(64), 0, s, L, static_cast<int>(FP),
+                       static_cast<int>(k), S, KP);
+    if (nb - k - 1 > 0)
+      hipLaunchKernelGGL(ridge_trsv_update_kernel, dim3(nb - k - 1, ncb), dim3(256), 0, s, L,
+                         static_cast<int>(FP), static_cast<int>(k), 0, S, KP);
+  }
+  for (int64_t k = nb - 1; k >= 0; k--) {  // L^T W = Y
+    hipLaunchKernelGGL(ridge_trsv_bwd_diag_kernel, dim3(ncb), dim3(64), 0, s, L, static_cast<int>(FP),
+                       static_cast<int>(k), S, KP, t->err_flag.ptr);
+    if (k > 0)
+      hipLaunchKernelGGL(ridge_trsv_update_kernel, dim3(k, ncb), dim3(256), 0, s, L, static_cast<int>(FP),
+                         static_cast<int>(k), 1, S, KP);
+  }
+  hipLaunchKernelGGL(ridge_commit_kernel, dim3(ceil_div(F * KP, 256)), dim3(256), 0, s, S, F * KP,
+                     t->err_flag.ptr, t->f_W[which].ptr);
+  t->prof.end(s);
+  IRS_HIP(hipGetLastError());
+}
+
+// step_with_prior's check, hpp:639-653: an empty row whose system would be singular
+bool prior_undefined(irs_ials_trainer *t, int which) {
+  if (t->cfg.alpha0 != 0.0f) return false;
+  const float empty_reg = t->cfg.reg * std::pow(t->cfg.alpha0 * static_cast<float>(t->rows_of(1 - which)) + 0,
+                                                t->cfg.nu);
+  return (!(empty_reg > 0.0f) || !std::isfinite(empty_reg)) && t->side[which].has_empty;
+}
+
+}  // namespace
+
 irs_status irs_ials_set_features(irs_ials_trainer *t, int32_t which, int64_t rows, int64_t n_feat,
                                  const int64_t *indptr, const int32_t *indices,
                                  const float *data) {
@@ -2376,6 +2511,7 @@ irs_status irs_ials_set_features(irs_ials_trainer *t, int32_t which, int64_t row
     if (F.unit) t->ft_data[which].upload(ones, s);
     else t->ft_data[which].upload(Ft.data, s);
     t->f_W[which].alloc(static_cast<size_t>(std::max<int64_t>(n_feat, 1)) * t->KP);
+    t->f_W[which].zero(s);  // the weights start at zero (initialize_feature_aware, hpp:1013-1014)
     t->f_rhs[which].alloc(static_cast<size_t>(std::max<int64_t>(n_feat, 1)) * t->KP);
     int64_t longest = 1;
     for (int64_t f = 0; f < n_feat; f++) longest = std::max(longest, Ft.indptr[f + 1] - Ft.indptr[f]);
@@ -2384,6 +2520,8 @@ irs_status irs_ials_set_features(irs_ials_trainer *t, int32_t which, int64_t row
                            t->KP);
     IRS_HIP(hipStreamSynchronize(s));  // host vectors go out of scope
     t->n_feat[which] = n_feat;
+    t->w_rows[which] = n_feat;
+    t->ridge_ready[which] = false;  // the cached Gram / LLT belonged to the old features
   });
 }
 
@@ -2392,18 +2530,12 @@ irs_status irs_ials_apply_feature_prior(irs_ials_trainer *t, int32_t which, cons
     check_arg(t && weight && (which == 0 || which == 1), "bad argument.");
     check_arg(t->n_feat[which] > 0, "no feature matrix was set for this side.");
     IRS_HIP(hipSetDevice(t->device));
-    const int64_t F = t->n_feat[which], n = t->rows_of(which);
+    const int64_t F = t->n_feat[which];
     std::vector<float> padded(static_cast<size_t>(F) * t->KP, 0.0f);
     for (int64_t f = 0; f < F; f++)
       std::copy(weight + f * t->K, weight + (f + 1) * t->K, padded.begin() + f * t->KP);
     t->f_W[which].upload(padded, t->stream);
-    t->prior[which].alloc(static_cast<size_t>(ceil_div(n, 8) * 8) * t->KP);
-    t->prof.begin(which == 0 ? "feature_prior_user" : "feature_prior_item", t->stream);
-    hipLaunchKernelGGL(feature_prior_kernel, dim3(ceil_div(n, 4), ceil_div(t->KP, 256)), dim3(256), 0, t->stream,
-                       t->f_indptr[which].ptr, t->f_indices[which].ptr, t->f_data[which].ptr,
-                       t->f_W[which].ptr, n, t->KP, t->prior[which].ptr);
-    t->prof.end(t->stream);
-    IRS_HIP(hipGetLastError());
+    launch_feature_prior(t, which);
     IRS_HIP(hipStreamSynchronize(t->stream));  // `padded` goes out of scope
     t->has_prior[which] = true;
   });
@@ -2416,21 +2548,96 @@ irs_status irs_ials_feature_rhs(irs_ials_trainer *t, int32_t which, float *out) 
     require_X(t);
     IRS_HIP(hipSetDevice(t->device));
     const int64_t F = t->n_feat[which];
-    t->prof.begin(which == 0 ? "feature_rhs_user" : "feature_rhs_item", t->stream);
-    const int nc = t->f_chunks[which];
-    hipLaunchKernelGGL(feature_rhs_kernel, dim3(F, nc, ceil_div(t->KP, 256)), dim3(256), 0, t->stream,
-                       t->ft_indptr[which].ptr, t->ft_indices[which].ptr, t->ft_data[which].ptr,
-                       t->side[which].reg.ptr, t->factor[which].ptr, t->KP,
-                       static_cast<int>(FEATURE_RHS_CHUNK), static_cast<int>(F),
-                       t->f_part[which].ptr);
-    hipLaunchKernelGGL(feature_rhs_reduce_kernel, dim3(ceil_div(F * t->KP, 256)), dim3(256), 0,
-                       t->stream, t->f_part[which].ptr, nc, F * t->KP, t->f_rhs[which].ptr);
-    t->prof.end(t->stream);
-    IRS_HIP(hipGetLastError());
+    launch_feature_rhs(t, which, t->f_rhs[which].ptr);
     IRS_HIP(hipMemcpy2DAsync(out, t->K * sizeof(float), t->f_rhs[which].ptr,
                              t->KP * sizeof(float), t->K * sizeof(float), F,
                              hipMemcpyDeviceToHost, t->stream));
     IRS_HIP(hipStreamSynchronize(t->stream));
+  });
+}
+
+// IALSTrainer::step of a feature-aware trainer, hpp:758-789
+irs_status irs_ials_feature_step(irs_ials_trainer *t, const irs_ials_solver_config *sc) {
+  return guard([&] {
+    check_arg(t != nullptr, "null trainer.");
+    check_solver(sc);
+    if (sc->solver_type == IRS_SOLVER_IALSPP)  // hpp:759-761
+      throw std::invalid_argument("Feature-aware iALS does not support IALSPP.");
+    require_X(t);
+    check_arg(t->whole && t->shard.user_begin == 0 && t->shard.user_end == t->n_users &&
+                  t->shard.item_begin == 0 && t->shard.item_end == t->n_items,
+              "irs_ials_feature_step needs an unsharded trainer.");
+    IRS_HIP(hipSetDevice(t->device));
+    if (t->epoch < static_cast<int64_t>(t->cfg.feature_warmup_epochs)) {  // hpp:784-788
+      plain_epoch(t, sc);
+      sync_and_check(t);
+      t->epoch++;
+      return;
+    }
+    bool built[2] = {false, false};
+    try {
+      for (int w = 0; w < 2; w++) {  // hpp:763-780
+        full_gramian(t, w);
+        if (t->n_feat[w] > 0) {
+          if (prior_undefined(t, w)) {
+            if (w == 1) sync_and_check(t);  // (the user half stands, as in the reference)
+            throw std::invalid_argument(
+                "Feature-prior embedding is not uniquely defined for an empty interaction row when "
+                "alpha0 and its regularization are zero.");
+          }
+          launch_feature_prior(t, w);
+          launch_solve(t, t->side[w], t->factor[1 - w].ptr, t->factor[w].ptr, w, sc, t->prior[w].ptr);
+          if (!t->ridge_ready[w]) {
+            launch_ridge_factorize(t, w);
+            built[w] = true;
+          }
+          launch_ridge_solve(t, w);
+        } else {
+          launch_solve(t, t->side[w], t->factor[1 - w].ptr, t->factor[w].ptr, w, sc);
+        }
+      }
+      sync_and_check(t);
+    } catch (...) {
+      for (int w = 0; w < 2; w++)
+        if (built[w]) t->ridge_ready[w] = false;
+      throw;
+    }
+    for (int w = 0; w < 2; w++)
+      if (built[w]) t->ridge_ready[w] = true;
+    t->epoch++;
+  });
+}
+
+// `.user_feature_weight` / `.item_feature_weight` (als/wrapper.cpp:160-161)
+irs_status irs_ials_get_feature_weight(irs_ials_trainer *t, int32_t which, float *out) {
+  return guard([&] {
+    check_arg(t && (which == 0 || which == 1), "bad argument.");
+    const int64_t F = t->w_rows[which];
+    if (F == 0) return;
+    check_arg(out != nullptr, "null argument.");
+    IRS_HIP(hipSetDevice(t->device));
+    IRS_HIP(hipMemcpy2DAsync(out, t->K * sizeof(float), t->f_W[which].ptr, t->KP * sizeof(float),
+                             t->K * sizeof(float), F, hipMemcpyDeviceToHost, t->stream));
+    IRS_HIP(hipStreamSynchronize(t->stream));
+  });
+}
+
+irs_status irs_ials_set_feature_weight(irs_ials_trainer *t, int32_t which, const float *in, int64_t rows,
+                                       int64_t cols) {
+  return guard([&] {
+    check_arg(t && (which == 0 || which == 1), "bad argument.");
+    check_arg(rows >= 0 && cols == t->K, "feature weights must have K columns.");
+    check_arg(t->n_feat[which] == 0 || rows == t->n_feat[which],
+              "feature weights must have one row per feature column.");
+    check_arg(rows == 0 || in != nullptr, "null argument.");
+    IRS_HIP(hipSetDevice(t->device));
+    t->f_W[which].alloc(static_cast<size_t>(std::max<int64_t>(rows, 1)) * t->KP);
+    t->f_W[which].zero(t->stream);
+    if (rows > 0)
+      IRS_HIP(hipMemcpy2DAsync(t->f_W[which].ptr, t->KP * sizeof(float), in, t->K * sizeof(float),
+                               t->K * sizeof(float), rows, hipMemcpyHostToDevice, t->stream));
+    IRS_HIP(hipStreamSynchronize(t->stream));
+    t->w_rows[which] = rows;
   });
 }
 

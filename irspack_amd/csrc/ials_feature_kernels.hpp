@@ -1,7 +1,8 @@
 // Feature-aware iALS, device side of the two feature products (IALSTrainer.hpp:702-708,
 // 1134-1171): the prior  features @ W  that enters the per-row solves, and the right-hand side
 // features^T (D factor)  of the feature-weight ridge system (D = diag of the per-row
-// regularisers).  The F x F ridge solve itself stays on the host (see _ials_core.py).
+// regularisers).  The F x F ridge system is formed, factorised and solved on the device too
+// (ials_ridge_kernels.hpp, irs_ials_feature_step).
 #pragma once
 #include "ials_kernels.hpp"
 

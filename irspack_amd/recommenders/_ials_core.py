@@ -327,8 +327,6 @@ class IALSTrainer:
                 raise ValueError("Feature weight regularization must be positive.")
             self._feature_aware = True
             self._features = [uf, itf]
-            self._ufw = np.zeros((uf.shape[1], self._K), dtype=np.float32)
-            self._ifw = np.zeros((itf.shape[1], self._K), dtype=np.float32)
             Xc = sps.csr_matrix(X)
             self._row_nnz = [np.diff(Xc.indptr), np.bincount(Xc.indices, minlength=self._n_items)]
             for side, F in enumerate(self._features):  # the products with F run on the device
@@ -339,21 +337,43 @@ class IALSTrainer:
                     check(lib().irs_ials_set_features(
                         self._h, C.c_int32(side), C.c_int64(Fc.shape[0]), C.c_int64(Fc.shape[1]),
                         ptr(fp, C.c_int64), ptr(fi, C.c_int32), ptr(fd, C.c_float)))
+                    self._n_feat[side] = self._w_rows[side] = int(F.shape[1])
+                    self._w_cache[side] = None  # zero on the device
 
     def _empty_feature_weight(self) -> None:
-        self._ufw = np.zeros((0, self._K), dtype=np.float32)
-        self._ifw = np.zeros((0, self._K), dtype=np.float32)
+        # the feature weights live on the device (irs_ials_get / set_feature_weight); _w_cache
+        # holds the host copy until the next step or assignment
+        self._n_feat = [0, 0]
+        self._w_rows = [0, 0]
+        self._w_cache: List[Optional[np.ndarray]] = [np.zeros((0, self._K), dtype=np.float32)] * 2
         self._feature_aware = False
         self._features = [None, None]
         self._row_nnz = [None, None]
         self._ridge_cache = [None, None]
         self._epoch = 0
 
-    # -- feature-aware pieces (hpp:758-789, 1052-1209).  The per-row solves run on the GPU
-    #    with the prior added to the right-hand side; the F x F feature-weight ridge system
-    #    is a small host solve in float32 like the reference's.
+    # -- feature-aware pieces (hpp:758-789, 1052-1209).  `step` runs the whole feature-aware
+    #    epoch in the library (irs_ials_feature_step); the host pieces below serve
+    #    `_step_host_ridge`, the earlier host-driven sequence kept for A/B tests, and compute_loss.
     def _weight(self, side: int) -> np.ndarray:
-        return self._ufw if side == 0 else self._ifw
+        W = self._w_cache[side]
+        if W is None:
+            W = np.zeros((self._w_rows[side], self._K), dtype=np.float32)
+            if W.shape[0]:
+                check(lib().irs_ials_get_feature_weight(self._h, C.c_int32(side), ptr(W, C.c_float)))
+            self._w_cache[side] = W
+        return W
+
+    def _set_weight(self, side: int, value: Any) -> None:
+        value = np.asarray(value, dtype=np.float32)
+        value = value.reshape(0, self._K) if value.ndim != 2 else np.ascontiguousarray(value)
+        if value.shape[1] == self._K and (self._n_feat[side] == 0 or value.shape[0] == self._n_feat[side]):
+            check(lib().irs_ials_set_feature_weight(self._h, C.c_int32(side), ptr(value, C.c_float),
+                                                    C.c_int64(value.shape[0]), C.c_int64(value.shape[1])))
+            self._w_rows[side] = int(value.shape[0])
+        # (a matrix of another shape is no weight matrix of this trainer: it stays on the host,
+        # where transform_*_feature rejects it like the reference)
+        self._w_cache[side] = value.copy()
 
     def _row_reg(self, side: int, nnz: np.ndarray) -> np.ndarray:
         """Solver::compute_reg (hpp:117-120) in float32 for every row."""
@@ -408,10 +428,7 @@ class IALSTrainer:
             sol = sla.cho_solve(chol, rhs, check_finite=False).astype(np.float32)
         if not np.isfinite(sol).all():
             raise RuntimeError("Feature ridge solve failed.")
-        if side == 0:
-            self._ufw = sol
-        else:
-            self._ifw = sol
+        self._set_weight(side, sol)
 
     @classmethod
     def _from_factors(
@@ -459,6 +476,18 @@ class IALSTrainer:
 
     # -- training / scoring -------------------------------------------------
     def step(self, solver_config: IALSSolverConfig) -> None:
+        sc = solver_config._struct()
+        if self._feature_aware:  # hpp:758-789 in one library call, ridge update on the device
+            self._w_cache = [None, None]
+            check(lib().irs_ials_feature_step(self._h, C.byref(sc)))
+        else:
+            check(lib().irs_ials_step(self._h, C.byref(sc)))
+        self._epoch += 1
+
+    def _step_host_ridge(self, solver_config: IALSSolverConfig) -> None:
+        """The host-driven feature-aware epoch (prior and per-row solves on the device, the F x F
+        ridge solve in scipy), for A/B tests against ``step``.  Its epochs are counted here only:
+        the library's epoch counter (the warm-up of ``step``) advances on plain epochs alone."""
         sc = solver_config._struct()
         if self._feature_aware and solver_config.solver_type == SolverType.IALSPP:
             raise ValueError("Feature-aware iALS does not support IALSPP.")  # hpp:759-761
@@ -624,34 +653,32 @@ class IALSTrainer:
 
     @property
     def user_feature_weight(self) -> np.ndarray:
-        return self._ufw
+        return self._weight(0).copy()
 
     @user_feature_weight.setter
     def user_feature_weight(self, value: np.ndarray) -> None:
-        value = np.asarray(value, dtype=np.float32)
-        self._ufw = value.reshape(0, self._K) if value.ndim != 2 else np.ascontiguousarray(value)
+        self._set_weight(0, value)
 
     @property
     def item_feature_weight(self) -> np.ndarray:
-        return self._ifw
+        return self._weight(1).copy()
 
     @item_feature_weight.setter
     def item_feature_weight(self, value: np.ndarray) -> None:
-        value = np.asarray(value, dtype=np.float32)
-        self._ifw = value.reshape(0, self._K) if value.ndim != 2 else np.ascontiguousarray(value)
+        self._set_weight(1, value)
 
     # -- pickle: (config, user, item, ufw, ifw); 3- or 5-tuples accepted
     #    (wrapper.cpp:162-181).  The restored object has no interaction matrix.
     def __getstate__(self) -> tuple:
-        return (self._config, self.user, self.item, self._ufw, self._ifw)
+        return (self._config, self.user, self.item, self.user_feature_weight, self.item_feature_weight)
 
     def __setstate__(self, state: tuple) -> None:
         if len(state) not in (3, 5):
             raise RuntimeError("Invalid IALSTrainer pickle state.")
         self._restore(state[0], state[1], state[2])
         if len(state) == 5:
-            self._ufw = np.asarray(state[3], dtype=np.float32)
-            self._ifw = np.asarray(state[4], dtype=np.float32)
+            self._set_weight(0, state[3])
+            self._set_weight(1, state[4])
 
     # -- device-level access for the multi-GPU host loop and the benchmark ----
     def set_stream(self, hip_stream: int) -> None:
