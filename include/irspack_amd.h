@@ -4,8 +4,8 @@
  *
  * Every entry point below is what the reference's FFI for this path binds
  * (nanobind modules `irspack.recommenders._ials_core`, `._knn`,
- * `irspack.evaluation._core_evaluator`, and `remove_diagonal` of
- * `irspack.utils._util_cpp`); the reference interface each one replaces is
+ * `irspack.evaluation._core_evaluator`, and `remove_diagonal` and the SLIM
+ * coordinate descent of `irspack.utils._util_cpp`); the reference interface each one replaces is
  * cited as file:line relative to /root/reference.
  *
  * Conventions
@@ -472,6 +472,42 @@ typedef struct irs_eval_stats {
                           * (includes the gaps in which the host reads the hard-row list back) */
 } irs_eval_stats;
 irs_status irs_eval_last_stats(irs_evaluator *e, irs_eval_stats *out);
+
+/* ------------------------------------------------------------------ SLIM
+ * slim_weight_positive_only / slim_weight_allow_negative of irspack.utils._util_cpp
+ * (cpp_source/util.cpp:31-40, the coordinate descent of cpp_source/util.hpp:228-424; the caller is
+ * src/irspack/recommenders/slim.py).  For every target item j, by cyclic coordinate descent from w = 0
+ * on the item Gram matrix G = X^T X (dense fp32 on the device):
+ *     min_w  1/2 |x_j - X w|^2 + l2/2 |w|^2 + l1 |w|_1,   w_j = 0   [w >= 0 when positive_only]
+ * with the update of util.hpp:300-345, at most n_iter sweeps, a column stopping after the first sweep
+ * whose largest coefficient change is < tol (util.hpp:346-351, here per column, the reference per SIMD
+ * block of columns).  Where the reference is not a function of its arguments this library is: the
+ * coordinate order of every sweep is the ascending one (the reference shuffles with a per-thread
+ * generator shared by the blocks a thread happens to fetch, util.hpp:251,293), so the result is
+ * bit-identical from call to call; a coordinate with G_ff + l2 == 0 keeps the coefficient 0.
+ * top_k >= 0: a column with more non-zeros keeps its top_k largest VALUES (not magnitudes,
+ * util.hpp:383-392; ties: the lower row index); top_k < 0: no limit.
+ * X is CSR float32 [rows, cols], validated on the host: monotone indptr, column indices in range and
+ * strictly ascending within a row - a duplicate column index is IRS_INVALID_ARGUMENT, not summed.
+ * Argument checks and messages: util.hpp:233-236 (n_iter > 0, l2_coeff >= 0, l1_coeff >= 0); they come
+ * before any device work.  IRS_RUNTIME_ERROR when 8 cols^2 bytes (G and the dense coefficients) plus
+ * working space exceed the free device memory.
+ * The result [cols, cols] is held by the handle as CSC: col_ptr int64[cols + 1], indices (rows, ascending)
+ * int32[nnz], data float32[nnz]; no stored zeros, empty diagonal.  The fetch arrays are caller-owned
+ * (sizes from the nnz call). */
+typedef struct irs_slim_result irs_slim_result;
+irs_status irs_slim_fit(int64_t rows, int64_t cols, const int64_t *indptr, const int32_t *indices,
+                        const float *data, int32_t positive_only, int64_t n_iter, float l2_coeff,
+                        float l1_coeff, float tol, int64_t top_k, int32_t device,
+                        irs_slim_result **out);
+irs_status irs_slim_nnz(irs_slim_result *r, int64_t *nnz);
+irs_status irs_slim_fetch(irs_slim_result *r, int64_t *col_ptr, int32_t *indices, float *data);
+/* Measurement only: device milliseconds (HIP events) of the three phases - Gram matrix (with the upload
+ * and the transpose), descent, emit - the sweeps run summed over the columns, and the coordinate
+ * changes applied (one axpy over a column of G each).  Any pointer may be NULL. */
+irs_status irs_slim_last_stats(irs_slim_result *r, double *gram_ms, double *descent_ms,
+                               double *emit_ms, int64_t *sweeps_total, int64_t *updates_total);
+irs_status irs_slim_destroy(irs_slim_result *r);
 
 /* ------------------------------------------------------------ measurement
  * No reference counterpart: SURVEY.md 8(d) asks for ceilings MEASURED on the box next to the

@@ -145,6 +145,11 @@ EXPORTED_SYMBOLS = [
     "irs_knn_last_walked",
     "irs_remove_diagonal",
     "irs_retrieve_recommend",
+    "irs_slim_fit",
+    "irs_slim_nnz",
+    "irs_slim_fetch",
+    "irs_slim_last_stats",
+    "irs_slim_destroy",
     "irs_eval_create",
     "irs_eval_destroy",
     "irs_eval_get_metrics",
@@ -157,11 +162,19 @@ EXPORTED_SYMBOLS = [
     "irs_measure_ceilings",
 ]
 
-# argument types of the feature-aware step and its weight accessors (irs_status return)
+# argument types of the feature-aware step, its weight accessors and the SLIM calls (irs_status return)
 ARGTYPES = {
     "irs_ials_feature_step": [C.c_void_p, C.c_void_p],
     "irs_ials_get_feature_weight": [C.c_void_p, C.c_int32, C.POINTER(C.c_float)],
     "irs_ials_set_feature_weight": [C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_int64, C.c_int64],
+    "irs_slim_fit": [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                     C.c_int32, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int64, C.c_int32,
+                     C.POINTER(C.c_void_p)],
+    "irs_slim_nnz": [C.c_void_p, C.POINTER(C.c_int64)],
+    "irs_slim_fetch": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float)],
+    "irs_slim_last_stats": [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                            C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "irs_slim_destroy": [C.c_void_p],
 }
 
 _lib: Optional[C.CDLL] = None

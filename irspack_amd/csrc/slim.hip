@@ -1,0 +1,271 @@
+// SLIM: elastic-net coordinate descent per target item on the device (the reference's
+// cpp_source/util.hpp:228-424, bound as slim_weight_positive_only / slim_weight_allow_negative in
+// cpp_source/util.cpp:31-40).  Host side of the C ABI; the kernels are in slim_kernels.hpp.
+#include <algorithm>
+#include <chrono>
+#include <mutex>
+#include <numeric>
+
+#include "common.hpp"
+#include "slim_kernels.hpp"
+
+struct irs_slim_result {
+  int64_t cols = 0;
+  std::vector<int64_t> col_ptr;
+  std::vector<int32_t> indices;
+  std::vector<float> data;
+  double gram_ms = 0.0, descent_ms = 0.0, emit_ms = 0.0;
+  int64_t sweeps_total = 0, updates_total = 0;
+};
+
+namespace irs {
+namespace slim {
+
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() { IRS_HIP(hipEventCreate(&e)); }
+  ~Event() {
+    if (e) (void)hipEventDestroy(e);
+  }
+  Event(const Event &) = delete;
+  Event &operator=(const Event &) = delete;
+};
+
+static double elapsed_ms(const Event &a, const Event &b) {
+  float ms = 0.f;
+  IRS_HIP(hipEventElapsedTime(&ms, a.e, b.e));
+  return static_cast<double>(ms);
+}
+
+// the large dynamic-LDS limit of a descent kernel is raised once per kernel and device, not per launch
+template <class K> static void allow_dynamic_lds(K kernel, int which, int device, int bytes) {
+  static std::mutex mu;
+  static std::vector<uint32_t> done;  // per device: bit `which`
+  std::lock_guard<std::mutex> lock(mu);
+  if (done.size() <= static_cast<size_t>(device)) done.resize(static_cast<size_t>(device) + 1, 0u);
+  if (done[device] & (1u << which)) return;
+  IRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              bytes));
+  done[device] |= 1u << which;
+}
+
+static void fit(int64_t rows, int64_t cols, const int64_t *indptr, const int32_t *indices, const float *data,
+                bool positive_only, int64_t n_iter, float l2, float l1, float tol, int64_t top_k, int device,
+                irs_slim_result &res) {
+  res.cols = cols;
+  res.col_ptr.assign(static_cast<size_t>(cols) + 1, 0);
+  const int64_t nnz = indptr[rows];
+  // an empty matrix has G = 0: every candidate is -l1 / l2 <= 0 (or 0 / 0), every coefficient stays 0
+  if (cols == 0 || nnz == 0) return;
+  require_device(device);
+  hipStream_t s = nullptr;
+  hipDeviceProp_t prop;
+  IRS_HIP(hipGetDeviceProperties(&prop, device));
+  const int n_items = static_cast<int>(cols);
+  const size_t I = static_cast<size_t>(cols);
+
+  // where the running vector lives, and the launch shape that follows from it
+  const int lds_need = kSlotBytes + static_cast<int>(std::min<size_t>(I * 4, size_t(1) << 30));
+  const bool lds_r = env_flag("IRSPACK_AMD_SLIM_LDS", true) && I * 4 + kSlotBytes <= prop.sharedMemPerBlock;
+  const int lds_bytes = lds_r ? lds_need : kSlotBytes;
+  // few workgroups fit beside a large LDS image: make each one wide (every wave streams the axpy)
+  const int threads = lds_bytes > 80 * 1024 ? 1024 : lds_bytes > 40 * 1024 ? 512 : 256;
+  const int per_cu = std::max(1, std::min<int>(2048 / threads, static_cast<int>(prop.maxSharedMemoryPerMultiProcessor / std::max(lds_bytes, 1))));
+  const int n_wg = static_cast<int>(std::min<int64_t>(cols, int64_t(prop.multiProcessorCount) * std::min(per_cu, 4)));
+
+  // memory: G and the dense W (4 I^2 bytes each), the matrix twice, the q rows of the global path
+  size_t free_b = 0, total_b = 0;
+  IRS_HIP(hipMemGetInfo(&free_b, &total_b));
+  const double need = 8.0 * double(I) * double(I) + 16.0 * double(nnz) * 2.0 + 64.0 * double(I) +
+                      (lds_r ? 0.0 : 4.0 * double(I) * n_wg) + double(size_t(256) << 20);
+  if (need > double(free_b))
+    throw std::runtime_error("SLIM: the dense item Gram matrix and coefficient matrix of " + std::to_string(cols) +
+                             " items need " + std::to_string(static_cast<int64_t>(need / 1048576.0)) +
+                             " MiB of device memory, " + std::to_string(free_b >> 20) +
+                             " MiB are free (a sparse Gram path is not implemented).");
+
+  Event e0, e1, e2, e3;
+  IRS_HIP(hipEventRecord(e0.e, s));
+  // X by rows and by columns on the device
+  std::vector<int32_t> ip32(static_cast<size_t>(rows) + 1);
+  for (int64_t i = 0; i <= rows; i++) ip32[i] = static_cast<int32_t>(indptr[i]);
+  DeviceBuffer<int32_t> d_rptr, d_ridx, d_cptr, d_cidx, d_order;
+  DeviceBuffer<float> d_rval, d_cval;
+  DeviceBuffer<char> tmp;
+  d_rptr.upload(ip32, s);
+  d_ridx.upload(indices, static_cast<size_t>(nnz), s);
+  d_rval.upload(data, static_cast<size_t>(nnz), s);
+  d_cidx.alloc(static_cast<size_t>(nnz));
+  d_cval.alloc(static_cast<size_t>(nnz));
+  std::vector<int32_t> col_count;
+  transpose_csr_device(d_rptr.ptr, d_ridx.ptr, d_rval.ptr, rows, cols, nnz, d_cidx.ptr, d_cval.ptr, col_count, tmp, s);
+  std::vector<int32_t> cp32(I + 1, 0), order(I);
+  for (size_t f = 0; f < I; f++) cp32[f + 1] = cp32[f] + col_count[f];
+  // most popular columns first (Gram rows: the longest walk; descent: the most coordinate changes)
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return col_count[a] > col_count[b]; });
+  d_cptr.upload(cp32, s);
+  d_order.upload(order, s);
+
+  DeviceBuffer<float> d_G, d_W, d_diag, d_scratch;
+  d_G.alloc(I * I);
+  d_G.zero(s);
+  d_diag.alloc(I);
+  hipLaunchKernelGGL(gram_rows_kernel, dim3(static_cast<unsigned>(ceil_div(cols, 4))), dim3(256), 0, s,
+                     static_cast<const int32_t *>(d_rptr.ptr), static_cast<const int32_t *>(d_ridx.ptr),
+                     static_cast<const float *>(d_rval.ptr), static_cast<const int32_t *>(d_cptr.ptr),
+                     static_cast<const int32_t *>(d_cidx.ptr), static_cast<const float *>(d_cval.ptr),
+                     static_cast<const int32_t *>(d_order.ptr), n_items, d_G.ptr);
+  hipLaunchKernelGGL(gram_diag_kernel, dim3(static_cast<unsigned>(ceil_div(cols, 256))), dim3(256), 0, s,
+                     static_cast<const float *>(d_G.ptr), n_items, d_diag.ptr);
+  IRS_HIP(hipGetLastError());
+  IRS_HIP(hipEventRecord(e1.e, s));
+
+  // descent
+  d_W.alloc(I * I);
+  d_W.zero(s);
+  if (!lds_r) d_scratch.alloc(I * static_cast<size_t>(n_wg));
+  DeviceBuffer<int32_t> d_cursor;
+  DeviceBuffer<unsigned long long> d_stats;
+  d_cursor.alloc(1);
+  d_cursor.zero(s);
+  d_stats.alloc(2);
+  d_stats.zero(s);
+  auto launch = [&](auto kernel, int which) {
+    if (lds_bytes > 64 * 1024) allow_dynamic_lds(kernel, which, device, static_cast<int>(prop.sharedMemPerBlock));
+    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(n_wg)), dim3(static_cast<unsigned>(threads)),
+                       static_cast<size_t>(lds_bytes), s, static_cast<const float *>(d_G.ptr),
+                       static_cast<const float *>(d_diag.ptr), static_cast<const int32_t *>(d_order.ptr), n_items,
+                       n_iter, l2, l1, tol, d_W.ptr, d_scratch.ptr, d_cursor.ptr, d_stats.ptr);
+  };
+  if (positive_only) {
+    if (lds_r) launch(slim_descent_kernel<true, true>, 0);
+    else launch(slim_descent_kernel<true, false>, 1);
+  } else {
+    if (lds_r) launch(slim_descent_kernel<false, true>, 2);
+    else launch(slim_descent_kernel<false, false>, 3);
+  }
+  IRS_HIP(hipGetLastError());
+  IRS_HIP(hipEventRecord(e2.e, s));
+
+  // emit: counts, prefix sum, compaction; then one read-back of the arrays
+  DeviceBuffer<int32_t> d_raw, d_cnt, d_oidx;
+  DeviceBuffer<int64_t> d_colptr;
+  DeviceBuffer<float> d_oval;
+  d_raw.alloc(I);
+  d_cnt.alloc(I);
+  d_colptr.alloc(I + 1);
+  hipLaunchKernelGGL(slim_count_kernel, dim3(static_cast<unsigned>(cols)), dim3(256), 0, s,
+                     static_cast<const float *>(d_W.ptr), n_items, top_k, d_raw.ptr, d_cnt.ptr);
+  hipLaunchKernelGGL(slim_scan_kernel, dim3(1), dim3(1024), 0, s, static_cast<const int32_t *>(d_cnt.ptr), n_items,
+                     d_colptr.ptr);
+  IRS_HIP(hipGetLastError());
+  IRS_HIP(hipMemcpyAsync(res.col_ptr.data(), d_colptr.ptr, (I + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  IRS_HIP(hipStreamSynchronize(s));
+  const int64_t out_nnz = res.col_ptr[I];
+  if (out_nnz < 0 || static_cast<double>(out_nnz) > double(I) * double(I))
+    throw std::runtime_error("SLIM: inconsistent result size.");
+  res.indices.resize(static_cast<size_t>(out_nnz));
+  res.data.resize(static_cast<size_t>(out_nnz));
+  if (out_nnz > 0) {
+    d_oidx.alloc(static_cast<size_t>(out_nnz));
+    d_oval.alloc(static_cast<size_t>(out_nnz));
+    hipLaunchKernelGGL(slim_emit_kernel, dim3(static_cast<unsigned>(cols)), dim3(256), 0, s,
+                       static_cast<const float *>(d_W.ptr), n_items, static_cast<const int32_t *>(d_raw.ptr),
+                       static_cast<const int32_t *>(d_cnt.ptr), static_cast<const int64_t *>(d_colptr.ptr),
+                       d_oidx.ptr, d_oval.ptr);
+    IRS_HIP(hipGetLastError());
+  }
+  IRS_HIP(hipEventRecord(e3.e, s));
+  if (out_nnz > 0) {
+    IRS_HIP(hipMemcpyAsync(res.indices.data(), d_oidx.ptr, res.indices.size() * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, s));
+    IRS_HIP(hipMemcpyAsync(res.data.data(), d_oval.ptr, res.data.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+  }
+  unsigned long long stats[2] = {0, 0};
+  IRS_HIP(hipMemcpyAsync(stats, d_stats.ptr, sizeof(stats), hipMemcpyDeviceToHost, s));
+  IRS_HIP(hipStreamSynchronize(s));
+  res.gram_ms = elapsed_ms(e0, e1);
+  res.descent_ms = elapsed_ms(e1, e2);
+  res.emit_ms = elapsed_ms(e2, e3);
+  res.sweeps_total = static_cast<int64_t>(stats[0]);
+  res.updates_total = static_cast<int64_t>(stats[1]);
+}
+
+}  // namespace slim
+}  // namespace irs
+
+using namespace irs;
+
+extern "C" {
+
+irs_status irs_slim_fit(int64_t rows, int64_t cols, const int64_t *indptr, const int32_t *indices,
+                        const float *data, int32_t positive_only, int64_t n_iter, float l2_coeff, float l1_coeff,
+                        float tol, int64_t top_k, int32_t device, irs_slim_result **out) {
+  return guard([&] {
+    check_arg(out != nullptr, "out must not be null.");
+    *out = nullptr;
+    // util.hpp:233-236 (the reference's wording)
+    check_arg(n_iter > 0, "n_iter must be > 0.");
+    check_arg(l2_coeff >= 0, "l2_coeff must be > 0.");
+    check_arg(l1_coeff >= 0, "l1_coeff must be > 0.");
+    check_arg(rows >= 0 && cols >= 0 && indptr && indptr[0] == 0, "bad matrix.");
+    check_arg(rows < (int64_t(1) << 31) - 1 && cols < (int64_t(1) << 31) - 1, "rows and cols must be below 2^31.");
+    for (int64_t i = 0; i < rows; i++) check_arg(indptr[i + 1] >= indptr[i], "malformed indptr.");
+    const int64_t nnz = indptr[rows];
+    check_arg(nnz < (int64_t(1) << 31), "nnz must be below 2^31.");
+    check_arg(nnz == 0 || (indices && data), "bad matrix.");
+    // strictly ascending columns within a row: the Gram kernel's lanes must hit distinct elements
+    for (int64_t i = 0; i < rows; i++) {
+      int64_t prev = -1;
+      for (int64_t q = indptr[i]; q < indptr[i + 1]; q++) {
+        const int64_t c = indices[q];
+        check_arg(c >= 0 && c < cols, "column index out of range.");
+        check_arg(c != prev, "duplicate column index in a row (sum duplicates before the call).");
+        check_arg(c > prev, "column indices of a row must be sorted.");
+        prev = c;
+      }
+    }
+    auto res = std::make_unique<irs_slim_result>();
+    slim::fit(rows, cols, indptr, indices, data, positive_only != 0, n_iter, l2_coeff, l1_coeff, tol, top_k, device,
+              *res);
+    *out = res.release();
+  });
+}
+
+irs_status irs_slim_nnz(irs_slim_result *r, int64_t *nnz) {
+  return guard([&] {
+    check_arg(r && nnz, "null argument.");
+    *nnz = static_cast<int64_t>(r->indices.size());
+  });
+}
+
+irs_status irs_slim_fetch(irs_slim_result *r, int64_t *col_ptr, int32_t *indices, float *data) {
+  return guard([&] {
+    check_arg(r && col_ptr, "null argument.");
+    std::copy(r->col_ptr.begin(), r->col_ptr.end(), col_ptr);
+    if (!r->indices.empty()) {
+      check_arg(indices && data, "null argument.");
+      std::copy(r->indices.begin(), r->indices.end(), indices);
+      std::copy(r->data.begin(), r->data.end(), data);
+    }
+  });
+}
+
+irs_status irs_slim_last_stats(irs_slim_result *r, double *gram_ms, double *descent_ms, double *emit_ms,
+                               int64_t *sweeps_total, int64_t *updates_total) {
+  return guard([&] {
+    check_arg(r != nullptr, "null argument.");
+    if (gram_ms) *gram_ms = r->gram_ms;
+    if (descent_ms) *descent_ms = r->descent_ms;
+    if (emit_ms) *emit_ms = r->emit_ms;
+    if (sweeps_total) *sweeps_total = r->sweeps_total;
+    if (updates_total) *updates_total = r->updates_total;
+  });
+}
+
+irs_status irs_slim_destroy(irs_slim_result *r) {
+  return guard([&] { delete r; });
+}
+
+}  // extern "C"

@@ -5,10 +5,11 @@ from .base import BaseRecommender, BaseSimilarityRecommender, BaseUserSimilarity
 from .ials import IALSRecommender
 from .knn import (AsymmetricCosineKNNRecommender, CosineKNNRecommender, JaccardKNNRecommender,
                   P3alphaRecommender, RP3betaRecommender, TverskyIndexKNNRecommender)
+from .slim import SLIMRecommender
 from .user_knn import AsymmetricCosineUserKNNRecommender, CosineUserKNNRecommender
 
 __all__ = ["BaseRecommender", "BaseSimilarityRecommender", "IALSRecommender",
            "CosineKNNRecommender", "AsymmetricCosineKNNRecommender", "JaccardKNNRecommender",
            "TverskyIndexKNNRecommender", "P3alphaRecommender", "RP3betaRecommender",
            "BaseUserSimilarityRecommender", "CosineUserKNNRecommender",
-           "AsymmetricCosineUserKNNRecommender"]
+           "AsymmetricCosineUserKNNRecommender", "SLIMRecommender"]

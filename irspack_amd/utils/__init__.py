@@ -1,5 +1,6 @@
 """The pieces of the reference's ``irspack.utils._util_cpp`` that the kNN path calls
-(/root/reference/cpp_source/util.hpp:158-226, util.cpp:14,29-32).
+(/root/reference/cpp_source/util.hpp:158-226, util.cpp:14,29-32) and the SLIM coordinate descent
+(util.hpp:228-424, util.cpp:31-40).
 
 Everything goes through the C ABI: ``remove_diagonal``, the serving top-k
 ``retrieve_recommend_from_score`` and the two feature weightings (``irs_knn_weight``; the kNN
@@ -119,3 +120,77 @@ def retrieve_recommend_from_score(score, allowed_item_indices, cutoff: int, n_th
         return retrieve_recommend_from_score_f64(score, allowed_item_indices, cutoff, n_threads,
                                                  device=device)
     raise ValueError("Only float32 or float64 are allowed.")
+
+
+def _slim(X, positive_only: bool, n_threads: int, n_iter: int, l2_coeff: float, l1_coeff: float,
+          tol: float, top_k: int, device: Optional[int], stats: Optional[dict] = None) -> sps.csc_matrix:
+    # util.hpp:233-236, before any device work (the C call repeats the last three)
+    if n_threads <= 0:
+        raise ValueError("n_threads must be > 0.")
+    if n_iter <= 0:
+        raise ValueError("n_iter must be > 0.")
+    if l2_coeff < 0:
+        raise ValueError("l2_coeff must be > 0.")
+    if l1_coeff < 0:
+        raise ValueError("l1_coeff must be > 0.")
+    Xc = sps.csr_matrix(X, dtype=np.float32)
+    if not Xc.has_canonical_format:
+        Xc = Xc.copy()
+        Xc.sum_duplicates()  # (the C call rejects duplicate column indices within a row)
+    n_items = Xc.shape[1]
+    indptr = np.ascontiguousarray(Xc.indptr, dtype=np.int64)
+    indices = np.ascontiguousarray(Xc.indices, dtype=np.int32)
+    data = np.ascontiguousarray(Xc.data, dtype=np.float32)
+    if data.size == 0:
+        indices, data = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.float32)
+    handle = C.c_void_p()
+    check(lib().irs_slim_fit(
+        Xc.shape[0], n_items, ptr(indptr, C.c_int64), ptr(indices, C.c_int32), ptr(data, C.c_float),
+        1 if positive_only else 0, int(n_iter), float(l2_coeff), float(l1_coeff), float(tol), int(top_k),
+        _lib.default_device() if device is None else device, C.byref(handle)))
+    try:
+        nnz = C.c_int64()
+        check(lib().irs_slim_nnz(handle, C.byref(nnz)))
+        col_ptr = np.zeros(n_items + 1, dtype=np.int64)
+        rows = np.zeros(max(nnz.value, 1), dtype=np.int32)
+        vals = np.zeros(max(nnz.value, 1), dtype=np.float32)
+        check(lib().irs_slim_fetch(handle, ptr(col_ptr, C.c_int64), ptr(rows, C.c_int32), ptr(vals, C.c_float)))
+        if stats is not None:
+            g, d, e = C.c_double(), C.c_double(), C.c_double()
+            sw, up = C.c_int64(), C.c_int64()
+            check(lib().irs_slim_last_stats(handle, C.byref(g), C.byref(d), C.byref(e), C.byref(sw), C.byref(up)))
+            stats.update(gram_ms=g.value, descent_ms=d.value, emit_ms=e.value, sweeps_total=sw.value,
+                         updates_total=up.value)
+    finally:
+        lib().irs_slim_destroy(handle)
+    W = sps.csc_matrix((vals[:nnz.value], rows[:nnz.value], col_ptr), shape=(n_items, n_items))
+    W.has_sorted_indices = True
+    return W
+
+
+def slim_weight_allow_negative(X, n_threads: int, n_iter: int, l2_coeff: float, l1_coeff: float,
+                               tol: float, top_k: int = -1, *, device: Optional[int] = None) -> sps.csc_matrix:
+    """util.hpp:228-424 with ``positive_only = false`` (bound at util.cpp:31-35): for every item ``j`` the
+    elastic-net fit of column ``j`` on the other columns, ``min 1/2 |x_j - X w|^2 + l2/2 |w|^2 + l1 |w|_1``,
+    by cyclic coordinate descent from 0 on the device (``irs_slim_fit``).  Returns the ``I x I`` float32
+    ``csc_matrix`` with ``W[f, j] = w_f`` of target ``j``: sorted indices, no stored zeros, empty diagonal.
+
+    Where the reference's output depends on more than its arguments, this one does not:
+
+    * the coordinate order is the ascending one in every sweep (the reference shuffles with a per-thread
+      generator, so its unconverged output depends on ``n_threads`` and scheduling); the update is exact
+      Gauss-Seidel and the result is bit-identical from call to call.  ``n_threads`` is validated
+      (``> 0``) and otherwise ignored;
+    * every column stops on its own: after the first sweep whose largest coefficient change is ``< tol``
+      (the reference stops a SIMD-packet-sized block of columns together);
+    * a coordinate with ``G_ff + l2 == 0`` (an item without interactions, ``l2_coeff = 0``) gets 0.
+
+    ``top_k >= 0`` keeps the ``top_k`` largest values (not magnitudes) of a column that has more
+    non-zeros; ``-1`` keeps everything.  Duplicate entries of ``X`` are summed first."""
+    return _slim(X, False, n_threads, n_iter, l2_coeff, l1_coeff, tol, top_k, device)
+
+
+def slim_weight_positive_only(X, n_threads: int, n_iter: int, l2_coeff: float, l1_coeff: float,
+                              tol: float, top_k: int = -1, *, device: Optional[int] = None) -> sps.csc_matrix:
+    """:func:`slim_weight_allow_negative` under the constraint ``w >= 0`` (util.cpp:36-40)."""
+    return _slim(X, True, n_threads, n_iter, l2_coeff, l1_coeff, tol, top_k, device)
