@@ -509,6 +509,33 @@ irs_status irs_slim_last_stats(irs_slim_result *r, double *gram_ms, double *desc
                                double *emit_ms, int64_t *sweeps_total, int64_t *updates_total);
 irs_status irs_slim_destroy(irs_slim_result *r);
 
+/* ------------------------------------------------------------------ EASE / EDLAE
+ * DenseSLIMRecommender (src/irspack/recommenders/dense_slim.py:39-53) and EDLAERecommender
+ * (edlae.py:49-66): the closed-form item-item weights, float32 throughout, on the device:
+ *     G = X^T X,   P = G + diag(lam),  lam_j = diag_scale * G_jj + reg   (each operation rounded to
+ *     float32, no fused multiply-add: numpy's evaluation order),   B = P^-1,
+ *     W_ij = -B_ij / B_jj (i != j),  W_jj = 0.
+ * EASE passes diag_scale = 0, EDLAE float32(dropout_p / (1 - dropout_p)).  P is padded to a multiple of
+ * 64 with identity rows, factored P = L L^T (blocked fp32 MFMA Cholesky), inverted from the factor
+ * (L^-1, then B = L^-T L^-1 for the lower triangle) and finalized into W [cols, cols] row-major, which
+ * is caller-owned and written by one device-to-host copy.  Two calls give identical bytes.
+ * The matrix checks are irs_slim_fit's (IRS_INVALID_ARGUMENT, before any device work).  An empty matrix
+ * with reg > 0 gives W = 0 without device work.  IRS_RUNTIME_ERROR: 8 n_pad^2 bytes plus the matrix twice
+ * exceed the free device memory; or P is not positive definite (a pivot that is not > 0 or not finite;
+ * the message holds "not positive definite" and the first failing column) - W is then not written.
+ * Unlike the reference's LU inverse, an indefinite but non-singular P is an error. */
+typedef struct {
+  double gram_ms;     /* HIP events: upload, transpose, X^T X, diagonal */
+  double factor_ms;   /* P = L L^T */
+  double invert_ms;   /* L^-1 and B = L^-T L^-1 */
+  double finalize_ms; /* W from B */
+  double d2h_ms;      /* the copy into the caller's array */
+  int64_t n_pad;      /* padded order: cols rounded up to 64 */
+} irs_dense_slim_stats;
+irs_status irs_dense_slim_fit(int64_t rows, int64_t cols, const int64_t *indptr, const int32_t *indices,
+                              const float *data, float reg, float diag_scale, int32_t device, float *W,
+                              irs_dense_slim_stats *stats /* may be NULL */);
+
 /* ------------------------------------------------------------ measurement
  * No reference counterpart: SURVEY.md 8(d) asks for ceilings MEASURED on the box next to the
  * spec peaks.  Runs a 1 GiB device copy and STREAM triad (HBM bytes moved / time), a loop of

@@ -87,6 +87,17 @@ class CeilingsStruct(C.Structure):  # irs_ceilings
     ]
 
 
+class DenseSlimStatsStruct(C.Structure):  # irs_dense_slim_stats
+    _fields_ = [
+        ("gram_ms", C.c_double),
+        ("factor_ms", C.c_double),
+        ("invert_ms", C.c_double),
+        ("finalize_ms", C.c_double),
+        ("d2h_ms", C.c_double),
+        ("n_pad", C.c_int64),
+    ]
+
+
 ABI_VERSION = 4  # IRS_ABI_VERSION of include/irspack_amd.h
 # IRS_EXCHANGE_* of include/irspack_amd.h: how irs_ials_sharded_step moves the solved rows
 EXCHANGE_MODES = {"auto": 0, "broadcast": 1, "mesh": 2, "peer": 3}
@@ -150,6 +161,7 @@ EXPORTED_SYMBOLS = [
     "irs_slim_fetch",
     "irs_slim_last_stats",
     "irs_slim_destroy",
+    "irs_dense_slim_fit",
     "irs_eval_create",
     "irs_eval_destroy",
     "irs_eval_get_metrics",
@@ -175,6 +187,8 @@ ARGTYPES = {
     "irs_slim_last_stats": [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                             C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
     "irs_slim_destroy": [C.c_void_p],
+    "irs_dense_slim_fit": [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                           C.c_float, C.c_float, C.c_int32, C.POINTER(C.c_float), C.c_void_p],
 }
 
 _lib: Optional[C.CDLL] = None

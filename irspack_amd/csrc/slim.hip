@@ -4,9 +4,9 @@
 #include <algorithm>
 #include <chrono>
 #include <mutex>
-#include <numeric>
 
 #include "common.hpp"
+#include "gram_setup.hpp"
 #include "slim_kernels.hpp"
 
 struct irs_slim_result {
@@ -20,22 +20,6 @@ struct irs_slim_result {
 
 namespace irs {
 namespace slim {
-
-struct Event {
-  hipEvent_t e = nullptr;
-  Event() { IRS_HIP(hipEventCreate(&e)); }
-  ~Event() {
-    if (e) (void)hipEventDestroy(e);
-  }
-  Event(const Event &) = delete;
-  Event &operator=(const Event &) = delete;
-};
-
-static double elapsed_ms(const Event &a, const Event &b) {
-  float ms = 0.f;
-  IRS_HIP(hipEventElapsedTime(&ms, a.e, b.e));
-  return static_cast<double>(ms);
-}
 
 // the large dynamic-LDS limit of a descent kernel is raised once per kernel and device, not per launch
 template <class K> static void allow_dynamic_lds(K kernel, int which, int device, int bytes) {
@@ -86,36 +70,14 @@ static void fit(int64_t rows, int64_t cols, const int64_t *indptr, const int32_t
 
   Event e0, e1, e2, e3;
   IRS_HIP(hipEventRecord(e0.e, s));
-  // X by rows and by columns on the device
-  std::vector<int32_t> ip32(static_cast<size_t>(rows) + 1);
-  for (int64_t i = 0; i <= rows; i++) ip32[i] = static_cast<int32_t>(indptr[i]);
-  DeviceBuffer<int32_t> d_rptr, d_ridx, d_cptr, d_cidx, d_order;
-  DeviceBuffer<float> d_rval, d_cval;
-  DeviceBuffer<char> tmp;
-  d_rptr.upload(ip32, s);
-  d_ridx.upload(indices, static_cast<size_t>(nnz), s);
-  d_rval.upload(data, static_cast<size_t>(nnz), s);
-  d_cidx.alloc(static_cast<size_t>(nnz));
-  d_cval.alloc(static_cast<size_t>(nnz));
-  std::vector<int32_t> col_count;
-  transpose_csr_device(d_rptr.ptr, d_ridx.ptr, d_rval.ptr, rows, cols, nnz, d_cidx.ptr, d_cval.ptr, col_count, tmp, s);
-  std::vector<int32_t> cp32(I + 1, 0), order(I);
-  for (size_t f = 0; f < I; f++) cp32[f + 1] = cp32[f] + col_count[f];
-  // most popular columns first (Gram rows: the longest walk; descent: the most coordinate changes)
-  std::iota(order.begin(), order.end(), 0);
-  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return col_count[a] > col_count[b]; });
-  d_cptr.upload(cp32, s);
-  d_order.upload(order, s);
-
+  // X by rows and by columns on the device, G = X^T X
+  GramInput in;
+  DeviceBuffer<int32_t> &d_order = in.order;
   DeviceBuffer<float> d_G, d_W, d_diag, d_scratch;
   d_G.alloc(I * I);
   d_G.zero(s);
   d_diag.alloc(I);
-  hipLaunchKernelGGL(gram_rows_kernel, dim3(static_cast<unsigned>(ceil_div(cols, 4))), dim3(256), 0, s,
-                     static_cast<const int32_t *>(d_rptr.ptr), static_cast<const int32_t *>(d_ridx.ptr),
-                     static_cast<const float *>(d_rval.ptr), static_cast<const int32_t *>(d_cptr.ptr),
-                     static_cast<const int32_t *>(d_cidx.ptr), static_cast<const float *>(d_cval.ptr),
-                     static_cast<const int32_t *>(d_order.ptr), n_items, d_G.ptr);
+  upload_and_gram(rows, cols, indptr, indices, data, in, d_G.ptr, cols, s);
   hipLaunchKernelGGL(gram_diag_kernel, dim3(static_cast<unsigned>(ceil_div(cols, 256))), dim3(256), 0, s,
                      static_cast<const float *>(d_G.ptr), n_items, d_diag.ptr);
   IRS_HIP(hipGetLastError());
@@ -209,23 +171,7 @@ irs_status irs_slim_fit(int64_t rows, int64_t cols, const int64_t *indptr, const
     check_arg(n_iter > 0, "n_iter must be > 0.");
     check_arg(l2_coeff >= 0, "l2_coeff must be > 0.");
     check_arg(l1_coeff >= 0, "l1_coeff must be > 0.");
-    check_arg(rows >= 0 && cols >= 0 && indptr && indptr[0] == 0, "bad matrix.");
-    check_arg(rows < (int64_t(1) << 31) - 1 && cols < (int64_t(1) << 31) - 1, "rows and cols must be below 2^31.");
-    for (int64_t i = 0; i < rows; i++) check_arg(indptr[i + 1] >= indptr[i], "malformed indptr.");
-    const int64_t nnz = indptr[rows];
-    check_arg(nnz < (int64_t(1) << 31), "nnz must be below 2^31.");
-    check_arg(nnz == 0 || (indices && data), "bad matrix.");
-    // strictly ascending columns within a row: the Gram kernel's lanes must hit distinct elements
-    for (int64_t i = 0; i < rows; i++) {
-      int64_t prev = -1;
-      for (int64_t q = indptr[i]; q < indptr[i + 1]; q++) {
-        const int64_t c = indices[q];
-        check_arg(c >= 0 && c < cols, "column index out of range.");
-        check_arg(c != prev, "duplicate column index in a row (sum duplicates before the call).");
-        check_arg(c > prev, "column indices of a row must be sorted.");
-        prev = c;
-      }
-    }
+    slim::validate_csr(rows, cols, indptr, indices, data);
     auto res = std::make_unique<irs_slim_result>();
     slim::fit(rows, cols, indptr, indices, data, positive_only != 0, n_iter, l2_coeff, l1_coeff, tol, top_k, device,
               *res);

@@ -1,7 +1,7 @@
 // SLIM (elastic-net coordinate descent, cpp_source/util.hpp:228-424) on the item Gram matrix: the
 // device kernels of slim.hip.  DESIGN.md section 9 has the design and the measurements.
 //
-//   gram_rows_kernel      G = X^T X, dense I x I fp32, one wave per row of G
+//   gram_rows_kernel      G = X^T X, dense I x I fp32, one wave per row of G (gram_setup.hpp: EASE shares it)
 //   slim_descent_kernel   one persistent workgroup per target column; exact Gauss-Seidel in ascending
 //                         coordinate order, a chunk of blockDim.x coordinates evaluated at once
 //   count / scan / emit   the dense coefficient rows -> CSC arrays (top_k selection by value)
@@ -16,38 +16,6 @@ constexpr int kMaxWaves = 16;  // waves of a descent workgroup (1024 threads)
 // and the column handed out by the cursor; the running vector follows it (16-byte aligned, Guideline 17)
 constexpr int kSlotBytes = 2 * kMaxWaves * 8 + 2 * kMaxWaves * 4 + 16;
 static_assert(kSlotBytes % 16 == 0, "the running vector starts 16-byte aligned");
-
-// ---------------------------------------------------------------------------------------------- Gram
-// Row f of G = sum over the users u of column f of x_uf * X[u, :].  ONE wave owns the row and walks the
-// users in their stored (ascending) order; the 64 lanes take 64 entries of X[u, :] - distinct columns,
-// the host rejects duplicates - so every element of G is a sum in a fixed order: bit-identical from run
-// to run for any values (and exact for counts below 2^24).  A wave's loads and stores to one address
-// complete in program order, so the row is accumulated in place in global memory (it stays in L2).
-// `order` hands the longest columns out first.
-__global__ __launch_bounds__(256) void gram_rows_kernel(const int32_t *__restrict__ rptr,
-                                                        const int32_t *__restrict__ ridx,
-                                                        const float *__restrict__ rval,
-                                                        const int32_t *__restrict__ cptr,
-                                                        const int32_t *__restrict__ cidx,
-                                                        const float *__restrict__ cval,
-                                                        const int32_t *__restrict__ order, int32_t n_items,
-                                                        float *G) {
-  const int slot = static_cast<int>(blockIdx.x) * 4 + wave_index_in_block();
-  if (slot >= n_items) return;
-  const int lane = static_cast<int>(threadIdx.x & 63);
-  const int f = order[slot];
-  float *row = G + static_cast<int64_t>(f) * n_items;
-  const int p_end = cptr[f + 1];
-  for (int p = cptr[f]; p < p_end; p++) {
-    const int u = cidx[p];
-    const float xv = cval[p];
-    const int q_end = rptr[u + 1];
-    for (int q = rptr[u] + lane; q < q_end; q += 64) {
-      const int g = ridx[q];
-      row[g] += xv * rval[q];
-    }
-  }
-}
 
 __global__ void gram_diag_kernel(const float *__restrict__ G, int32_t n_items, float *__restrict__ diag) {
   const int f = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);

@@ -2,6 +2,8 @@
 the recommenders whose compiled core is rebuilt here."""
 
 from .base import BaseRecommender, BaseSimilarityRecommender, BaseUserSimilarityRecommender
+from .dense_slim import DenseSLIMRecommender
+from .edlae import EDLAERecommender
 from .ials import IALSRecommender
 from .knn import (AsymmetricCosineKNNRecommender, CosineKNNRecommender, JaccardKNNRecommender,
                   P3alphaRecommender, RP3betaRecommender, TverskyIndexKNNRecommender)
@@ -12,4 +14,5 @@ __all__ = ["BaseRecommender", "BaseSimilarityRecommender", "IALSRecommender",
            "CosineKNNRecommender", "AsymmetricCosineKNNRecommender", "JaccardKNNRecommender",
            "TverskyIndexKNNRecommender", "P3alphaRecommender", "RP3betaRecommender",
            "BaseUserSimilarityRecommender", "CosineUserKNNRecommender",
-           "AsymmetricCosineUserKNNRecommender", "SLIMRecommender"]
+           "AsymmetricCosineUserKNNRecommender", "SLIMRecommender", "DenseSLIMRecommender",
+           "EDLAERecommender"]

@@ -1,0 +1,34 @@
+"""``EDLAERecommender`` (irspack/recommenders/edlae.py): EASE with the dropout-derived diagonal, computed
+on the device by ``irspack_amd.utils.dense_slim_weight`` (``irs_dense_slim_fit``)."""
+
+from typing import Any
+
+import numpy as np
+
+from ..utils import dense_slim_weight
+from .base import BaseSimilarityRecommender
+
+
+class EDLAERecommender(BaseSimilarityRecommender):
+    r"""EDLAE (`Autoencoders that don't overfit towards the Identity
+    <https://proceedings.neurips.cc/paper/2020/hash/e33d974aae13e4d877477d51d8bafdc4-Abstract.html>`_),
+    the reference's edlae.py:49-66: EASE with
+
+    .. math ::
+
+        \lambda_j = \frac{p}{1 - p} (X^T X)_{jj} + \mathrm{reg}
+
+    on the diagonal, ``p = dropout_p``.  ``dropout_p == 1`` raises ``ZeroDivisionError`` (the expression
+    is the reference's).  Unlike the reference's LU inverse, ``dropout_p > 1`` (an indefinite system) raises
+    ``numpy.linalg.LinAlgError``: the inverse comes from a Cholesky factor."""
+
+    def __init__(self, X_train_all: Any, reg: float = 1.0, dropout_p: float = 0.1) -> None:
+        super().__init__(X_train_all)
+        self.reg = reg
+        self.dropout_p = dropout_p
+
+    def _learn(self) -> None:
+        q = 1 - self.dropout_p
+        # (a Python scalar times the float32 diagonal: the factor is rounded to float32 first)
+        diag_scale = np.float32(self.dropout_p / q)
+        self._W = dense_slim_weight(self.X_train_all, self.reg, diag_scale)

@@ -1,6 +1,7 @@
 """The pieces of the reference's ``irspack.utils._util_cpp`` that the kNN path calls
 (/root/reference/cpp_source/util.hpp:158-226, util.cpp:14,29-32) and the SLIM coordinate descent
-(util.hpp:228-424, util.cpp:31-40).
+(util.hpp:228-424, util.cpp:31-40); and the closed-form EASE / EDLAE weights (``dense_slim_weight``), which the
+reference computes with scipy inside ``recommenders/dense_slim.py`` and ``recommenders/edlae.py``.
 
 Everything goes through the C ABI: ``remove_diagonal``, the serving top-k
 ``retrieve_recommend_from_score`` and the two feature weightings (``irs_knn_weight``; the kNN
@@ -194,3 +195,43 @@ def slim_weight_positive_only(X, n_threads: int, n_iter: int, l2_coeff: float, l
                               tol: float, top_k: int = -1, *, device: Optional[int] = None) -> sps.csc_matrix:
     """:func:`slim_weight_allow_negative` under the constraint ``w >= 0`` (util.cpp:36-40)."""
     return _slim(X, True, n_threads, n_iter, l2_coeff, l1_coeff, tol, top_k, device)
+
+
+def dense_slim_weight(X, reg: float, diag_scale: float = 0.0, *, device: Optional[int] = None,
+                      stats: Optional[dict] = None) -> np.ndarray:
+    """The EASE / EDLAE item-item weights (dense_slim.py:39-53, edlae.py:49-66) on the device
+    (``irs_dense_slim_fit``), float32 throughout::
+
+        G = X^T X,  P = G + diag(diag_scale * diag(G) + reg),  B = P^-1,
+        W[i, j] = -B[i, j] / B[j, j]  (i != j),  W[j, j] = 0
+
+    Returns the C-contiguous float32 ``(I, I)`` array; two calls give identical bytes.  Duplicate entries
+    of ``X`` are summed first.  ``P`` is inverted from its Cholesky factor: a ``P`` that is not positive
+    definite raises ``numpy.linalg.LinAlgError`` (the reference's scipy LU inverse raises it for a singular
+    ``P`` only; an indefinite but non-singular ``P`` - ``dropout_p > 1``, a negative ``reg`` - is an error
+    here).  ``stats`` receives the phase times ``gram_ms, factor_ms, invert_ms, finalize_ms, d2h_ms`` (HIP
+    events) and the padded order ``n_pad``."""
+    Xc = sps.csr_matrix(X, dtype=np.float32)
+    if not Xc.has_canonical_format:
+        Xc = Xc.copy()
+        Xc.sum_duplicates()  # (the C call rejects duplicate column indices within a row)
+    n_items = Xc.shape[1]
+    indptr = np.ascontiguousarray(Xc.indptr, dtype=np.int64)
+    indices = np.ascontiguousarray(Xc.indices, dtype=np.int32)
+    data = np.ascontiguousarray(Xc.data, dtype=np.float32)
+    if data.size == 0:
+        indices, data = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.float32)
+    W = np.empty((n_items, n_items), dtype=np.float32)
+    st = _lib.DenseSlimStatsStruct()
+    status = lib().irs_dense_slim_fit(
+        Xc.shape[0], n_items, ptr(indptr, C.c_int64), ptr(indices, C.c_int32), ptr(data, C.c_float),
+        float(reg), float(diag_scale), _lib.default_device() if device is None else device,
+        W.ctypes.data_as(C.POINTER(C.c_float)), C.cast(C.byref(st), C.c_void_p))
+    if status == 2:
+        msg = lib().irs_last_error().decode("utf-8", "replace")
+        if "not positive definite" in msg:
+            raise np.linalg.LinAlgError(msg)
+    check(status)
+    if stats is not None:
+        stats.update({name: getattr(st, name) for name, _ in _lib.DenseSlimStatsStruct._fields_})
+    return W
