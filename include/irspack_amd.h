@@ -536,6 +536,50 @@ irs_status irs_dense_slim_fit(int64_t rows, int64_t cols, const int64_t *indptr,
                               const float *data, float reg, float diag_scale, int32_t device, float *W,
                               irs_dense_slim_stats *stats /* may be NULL */);
 
+/* ------------------------------------------------------------------ truncated SVD
+ * TruncatedSVDRecommender (src/irspack/recommenders/truncsvd.py: sklearn's randomized TruncatedSVD) - the
+ * device side of irspack_amd.utils.truncated_svd, float32.  A = X when n_users >= n_items, else X^T
+ * (sklearn's transpose="auto"): m x n with m >= n.  The handle keeps A, A^T and three m x l_pad blocks on the
+ * device (l_pad: the sketch width rounded up to 64, at most 576); the l x l symmetric eigenproblems between
+ * the calls are the caller's (float64 on the host).  One stream; one synchronisation per call, except that
+ * the first range call also sets the matrix up (blocking copies, the device transpose's synchronisation).  No
+ * float atomics, every sum has a fixed order: two runs give identical bytes.
+ *   create   validates X (CSR float32; the checks of irs_slim_fit, and every value finite) and keeps a copy;
+ *            the matrix reaches the device with the first range call, so every argument check of every call
+ *            comes before any device work (IRS_INVALID_ARGUMENT).
+ *   range    omega [rows, l] row-major is the Gaussian test matrix, rows == n (n_items when
+ *            n_users >= n_items, else n_users), 1 <= l <= min(n_users, n_items, 576).  Q = omega; n_iter times
+ *            { Y = A Q, normalise; Q = A^T Y, normalise }; Y = A Q.  Normalise: G = Y^T Y, Cholesky of
+ *            G + d I with d = 1e-5 trace(G) / l, Y <- Y L^-T.  gram_out [l, l] receives Y^T Y.
+ *   apply    Y <- Y m for m [l, l2] row-major, 1 <= l2 <= l; l becomes l2; gram_out [l2, l2] = Y^T Y.
+ *   project  Q = A^T Y (B^T for B = Y^T A); gram_out [l, l] = B B^T.
+ *   finish   rot [l, k] row-major, 1 <= k <= l: V = Q rot (A = X) or Y rot (A = X^T), the n_items x k side;
+ *            z = X V by one more product; every component's entry of largest magnitude is made positive
+ *            (sklearn's svd_flip on the rows of components_).  z_out [n_users, k], components_out [k, n_items].
+ * IRS_RUNTIME_ERROR: no device, not enough device memory, or a block whose Gram matrix has no Cholesky
+ * factor (a zero matrix; overflow). */
+typedef struct irs_truncsvd irs_truncsvd;
+typedef struct {
+  double setup_ms; /* HIP events, summed over the calls so far: upload, transpose, segment lists */
+  double spmm_ms;  /* the sparse x block products */
+  double gram_ms;  /* the Gram matrices of the blocks */
+  double chol_ms;  /* shift, Cholesky and triangular inverse of the l_pad x l_pad matrices */
+  double apply_ms; /* block x small-matrix products */
+  double d2h_ms;   /* copies into the caller's arrays */
+  double host_ms;  /* finish: signs and the transpose of the components on the host (host clock) */
+  int64_t n_spmm;  /* sparse x block products so far */
+  int64_t l_pad;
+} irs_truncsvd_stats_t;
+irs_status irs_truncsvd_create(int64_t n_users, int64_t n_items, const int64_t *indptr, const int32_t *indices,
+                               const float *data, int32_t device, irs_truncsvd **out);
+irs_status irs_truncsvd_range(irs_truncsvd *t, const float *omega, int64_t rows, int64_t l, int64_t n_iter,
+                              float *gram_out);
+irs_status irs_truncsvd_apply(irs_truncsvd *t, const float *m, int64_t l2, float *gram_out);
+irs_status irs_truncsvd_project(irs_truncsvd *t, float *gram_out);
+irs_status irs_truncsvd_finish(irs_truncsvd *t, const float *rot, int64_t k, float *z_out, float *components_out);
+irs_status irs_truncsvd_stats(irs_truncsvd *t, irs_truncsvd_stats_t *out);
+irs_status irs_truncsvd_destroy(irs_truncsvd *t);
+
 /* ------------------------------------------------------------ measurement
  * No reference counterpart: SURVEY.md 8(d) asks for ceilings MEASURED on the box next to the
  * spec peaks.  Runs a 1 GiB device copy and STREAM triad (HBM bytes moved / time), a loop of

@@ -98,6 +98,20 @@ class DenseSlimStatsStruct(C.Structure):  # irs_dense_slim_stats
     ]
 
 
+class TruncSvdStatsStruct(C.Structure):  # irs_truncsvd_stats_t
+    _fields_ = [
+        ("setup_ms", C.c_double),
+        ("spmm_ms", C.c_double),
+        ("gram_ms", C.c_double),
+        ("chol_ms", C.c_double),
+        ("apply_ms", C.c_double),
+        ("d2h_ms", C.c_double),
+        ("host_ms", C.c_double),
+        ("n_spmm", C.c_int64),
+        ("l_pad", C.c_int64),
+    ]
+
+
 ABI_VERSION = 4  # IRS_ABI_VERSION of include/irspack_amd.h
 # IRS_EXCHANGE_* of include/irspack_amd.h: how irs_ials_sharded_step moves the solved rows
 EXCHANGE_MODES = {"auto": 0, "broadcast": 1, "mesh": 2, "peer": 3}
@@ -162,6 +176,13 @@ EXPORTED_SYMBOLS = [
     "irs_slim_last_stats",
     "irs_slim_destroy",
     "irs_dense_slim_fit",
+    "irs_truncsvd_create",
+    "irs_truncsvd_range",
+    "irs_truncsvd_apply",
+    "irs_truncsvd_project",
+    "irs_truncsvd_finish",
+    "irs_truncsvd_stats",
+    "irs_truncsvd_destroy",
     "irs_eval_create",
     "irs_eval_destroy",
     "irs_eval_get_metrics",
@@ -189,6 +210,14 @@ ARGTYPES = {
     "irs_slim_destroy": [C.c_void_p],
     "irs_dense_slim_fit": [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float),
                            C.c_float, C.c_float, C.c_int32, C.POINTER(C.c_float), C.c_void_p],
+    "irs_truncsvd_create": [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                            C.c_int32, C.POINTER(C.c_void_p)],
+    "irs_truncsvd_range": [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_float)],
+    "irs_truncsvd_apply": [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_float)],
+    "irs_truncsvd_project": [C.c_void_p, C.POINTER(C.c_float)],
+    "irs_truncsvd_finish": [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float)],
+    "irs_truncsvd_stats": [C.c_void_p, C.c_void_p],
+    "irs_truncsvd_destroy": [C.c_void_p],
 }
 
 _lib: Optional[C.CDLL] = None

@@ -8,6 +8,7 @@ from .ials import IALSRecommender
 from .knn import (AsymmetricCosineKNNRecommender, CosineKNNRecommender, JaccardKNNRecommender,
                   P3alphaRecommender, RP3betaRecommender, TverskyIndexKNNRecommender)
 from .slim import SLIMRecommender
+from .truncsvd import TruncatedSVDRecommender
 from .user_knn import AsymmetricCosineUserKNNRecommender, CosineUserKNNRecommender
 
 __all__ = ["BaseRecommender", "BaseSimilarityRecommender", "IALSRecommender",
@@ -15,4 +16,4 @@ __all__ = ["BaseRecommender", "BaseSimilarityRecommender", "IALSRecommender",
            "TverskyIndexKNNRecommender", "P3alphaRecommender", "RP3betaRecommender",
            "BaseUserSimilarityRecommender", "CosineUserKNNRecommender",
            "AsymmetricCosineUserKNNRecommender", "SLIMRecommender", "DenseSLIMRecommender",
-           "EDLAERecommender"]
+           "EDLAERecommender", "TruncatedSVDRecommender"]

@@ -1,7 +1,9 @@
 """The pieces of the reference's ``irspack.utils._util_cpp`` that the kNN path calls
 (/root/reference/cpp_source/util.hpp:158-226, util.cpp:14,29-32) and the SLIM coordinate descent
 (util.hpp:228-424, util.cpp:31-40); and the closed-form EASE / EDLAE weights (``dense_slim_weight``), which the
-reference computes with scipy inside ``recommenders/dense_slim.py`` and ``recommenders/edlae.py``.
+reference computes with scipy inside ``recommenders/dense_slim.py`` and ``recommenders/edlae.py``; and the
+randomized truncated SVD (``truncated_svd``), which the reference takes from scikit-learn inside
+``recommenders/truncsvd.py``.
 
 Everything goes through the C ABI: ``remove_diagonal``, the serving top-k
 ``retrieve_recommend_from_score`` and the two feature weightings (``irs_knn_weight``; the kNN
@@ -235,3 +237,105 @@ def dense_slim_weight(X, reg: float, diag_scale: float = 0.0, *, device: Optiona
     if stats is not None:
         stats.update({name: getattr(st, name) for name, _ in _lib.DenseSlimStatsStruct._fields_})
     return W
+
+
+def _descending_eigh(G: np.ndarray):
+    """eigenvalues (descending) and eigenvectors of a symmetric matrix, float64"""
+    w, V = np.linalg.eigh(np.asarray(G, dtype=np.float64))
+    return w[::-1], V[:, ::-1]
+
+
+def truncated_svd(X, n_components: int, random_seed: int = 0, *, n_iter: int = 5, n_oversamples: int = 10,
+                  device: Optional[int] = None, stats: Optional[dict] = None):
+    """The randomized truncated SVD of ``sklearn.decomposition.TruncatedSVD(n_components, random_state=random_seed)``
+    (what truncsvd.py:79-83 of the reference fits) with the sparse and the tall dense products on the device
+    (``irs_truncsvd_*``), float32.  Returns ``(z, singular_values, components)``: ``(U, k)``, ``(k,)`` and
+    ``(k, I)`` float32, C-contiguous; ``z = X @ components.T``; in each row of ``components`` the entry of
+    largest magnitude is positive.  Two calls give identical bytes.
+
+    The Gaussian test matrix is sklearn's (``RandomState(random_seed).normal(size=(n, k + n_oversamples))``,
+    ``n = n_items`` when ``n_users >= n_items``, else ``n_users`` with ``X^T`` in the place of ``X``), cast to
+    float32 and clipped to its leading ``min(l, n_users, n_items)`` columns; the power iterations are
+    normalised by a shifted Cholesky factor instead of sklearn's LU, which spans the same subspace.  The
+    final basis is orthonormalised twice through the eigen-decomposition of its Gram matrix (float64, on the
+    host, eigenvalues ``<= 1e-6 * max`` dropped: rank revealing), the singular values and the rotation come
+    from the eigen-decomposition of ``B B^T``, ``B = Y^T A``.  A component past the numerical rank (the
+    basis has fewer columns than ``n_components``, or its eigenvalue of ``B B^T`` is not positive) is a zero
+    row with singular value 0.
+
+    ``stats`` receives the device phase times ``setup_ms, spmm_ms, gram_ms, chol_ms, apply_ms, d2h_ms`` (HIP
+    events), ``n_spmm``, ``l_pad``, the host times ``host_ms`` (signs and the transpose of the components inside the
+    last call), ``eigh_ms`` (the eigenproblems) and ``omega_ms`` (the test matrix)."""
+    import time
+
+    Xc = sps.csr_matrix(X, dtype=np.float32)
+    if not Xc.has_canonical_format:
+        Xc = Xc.copy()
+        Xc.sum_duplicates()  # (the C call rejects duplicate column indices within a row)
+    n_users, n_items = Xc.shape
+    k = int(n_components)
+    if k < 1:
+        raise ValueError("n_components must be >= 1.")
+    if k > n_items:
+        raise ValueError(f"n_components({k}) must be <= n_features({n_items}).")  # (sklearn's check)
+    if n_iter < 0 or n_oversamples < 0:
+        raise ValueError("n_iter and n_oversamples must be >= 0.")
+    z = np.zeros((n_users, k), dtype=np.float32)
+    sigma = np.zeros(k, dtype=np.float32)
+    comps = np.zeros((k, n_items), dtype=np.float32)
+    if stats is not None:
+        stats.update({name: 0 for name, _ in _lib.TruncSvdStatsStruct._fields_}, eigh_ms=0.0, omega_ms=0.0)
+    if n_users == 0 or not Xc.data.any():
+        return z, sigma, comps
+    t0 = time.perf_counter()
+    n = n_items if n_users >= n_items else n_users
+    l_full = k + int(n_oversamples)
+    l = min(l_full, n_users, n_items)
+    omega = np.random.RandomState(random_seed).normal(size=(n, l_full))
+    omega = np.ascontiguousarray(omega[:, :l], dtype=np.float32)
+    omega_ms = (time.perf_counter() - t0) * 1e3
+    indptr = np.ascontiguousarray(Xc.indptr, dtype=np.int64)
+    indices = np.ascontiguousarray(Xc.indices, dtype=np.int32)
+    data = np.ascontiguousarray(Xc.data, dtype=np.float32)
+    fptr = lambda a: ptr(a, C.c_float)  # noqa: E731
+    eigh_s = 0.0
+    handle = C.c_void_p()
+    check(lib().irs_truncsvd_create(n_users, n_items, ptr(indptr, C.c_int64), ptr(indices, C.c_int32), fptr(data),
+                                    _lib.default_device() if device is None else device, C.byref(handle)))
+    try:
+        G = np.empty((l, l), dtype=np.float32)
+        check(lib().irs_truncsvd_range(handle, fptr(omega), n, l, int(n_iter), fptr(G)))
+        for _ in range(2):  # Y <- Y V diag(w)^-1/2 over the eigenvalues that count
+            t = time.perf_counter()
+            w, V = _descending_eigh(G)
+            keep = w > 1e-6 * w[0]
+            M = np.ascontiguousarray(V[:, keep] / np.sqrt(w[keep]), dtype=np.float32)
+            eigh_s += time.perf_counter() - t
+            if M.shape[1] == 0:
+                return z, sigma, comps
+            G = np.empty((M.shape[1], M.shape[1]), dtype=np.float32)
+            check(lib().irs_truncsvd_apply(handle, fptr(M), M.shape[1], fptr(G)))
+        l2 = G.shape[0]
+        check(lib().irs_truncsvd_project(handle, fptr(G)))
+        t = time.perf_counter()
+        w, R = _descending_eigh(G)
+        kk = min(k, l2)
+        s = np.sqrt(np.maximum(w[:kk], 0.0))
+        live = s > 0
+        s = np.where(live, s, 0.0)
+        # A = X: V = B^T R / sigma;  A = X^T: the components are the rotated basis Y R itself
+        scale = np.where(live, 1.0 / np.where(live, s, 1.0), 0.0) if n_users >= n_items else live.astype(np.float64)
+        rot = np.ascontiguousarray(R[:, :kk] * scale, dtype=np.float32)
+        eigh_s += time.perf_counter() - t
+        zk = np.empty((n_users, kk), dtype=np.float32)
+        ck = np.empty((kk, n_items), dtype=np.float32)
+        check(lib().irs_truncsvd_finish(handle, fptr(rot), kk, fptr(zk), fptr(ck)))
+        z[:, :kk], comps[:kk], sigma[:kk] = zk, ck, s
+        if stats is not None:
+            st = _lib.TruncSvdStatsStruct()
+            check(lib().irs_truncsvd_stats(handle, C.cast(C.byref(st), C.c_void_p)))
+            stats.update({name: getattr(st, name) for name, _ in _lib.TruncSvdStatsStruct._fields_},
+                         eigh_ms=eigh_s * 1e3, omega_ms=omega_ms)
+    finally:
+        lib().irs_truncsvd_destroy(handle)
+    return z, sigma, comps
