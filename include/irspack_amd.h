@@ -580,6 +580,33 @@ irs_status irs_truncsvd_finish(irs_truncsvd *t, const float *rot, int64_t k, flo
 irs_status irs_truncsvd_stats(irs_truncsvd *t, irs_truncsvd_stats_t *out);
 irs_status irs_truncsvd_destroy(irs_truncsvd *t);
 
+/* ------------------------------------------------------------------ NMF
+ * NMFRecommender (src/irspack/recommenders/nmf.py: sklearn.decomposition.NMF, solver "cd", Frobenius loss,
+ * shuffle off) - the device side of irspack_amd.utils.nmf_fit / nmf_transform, float32.  X is CSR (float32,
+ * sorted, no duplicates, non-negative); W [n_users, k] and H [k, n_items] row-major hold the initial factors and
+ * receive the result (update_H = 0: H is read only, only W is fitted - sklearn's transform).  One iteration:
+ *     half(X, W, H^T, l1_W, l2_W), then, when update_H, half(X^T, H^T, W, l1_H, l2_H);
+ *     half(A, W, Ht, l1, l2):  G = Ht^T Ht, G[t, t] += l2;  XH = A Ht - l1;  for t = 0 .. k-1, every row i:
+ *         grad = sum_r G[t, r] W[i, r] - XH[i, t];  violation += W[i, t] == 0 ? |min(0, grad)| : |grad|;
+ *         if G[t, t] != 0: W[i, t] = max(W[i, t] - grad / G[t, t], 0)
+ * XH and G are summed in double and stored as float32; the violation is summed in double in a fixed order.  The loop stops when the first iteration's violation is 0,
+ * after the iteration whose violation / the first one's <= tol, or after max_iter iterations; n_iter receives
+ * the count, violations (NULL or double[max_iter]) the per-iteration sums.  No float atomics: two calls give
+ * identical bytes.  IRS_INVALID_ARGUMENT before any device work: the matrix checks of irs_truncsvd_create, a
+ * negative value, k < 1 or k > 576, max_iter < 1, tol < 0, a negative or non-finite regulariser, a non-finite or
+ * negative entry of the initial W or H.  IRS_RUNTIME_ERROR: no device, not enough device memory. */
+typedef struct {
+  double setup_ms; /* HIP events: upload, transpose, segment lists, the initial factors */
+  double spmm_ms;  /* the sparse x block products */
+  double gram_ms;  /* the k x k Gram matrices */
+  double sweep_ms; /* the coordinate sweeps */
+  double d2h_ms;   /* the violation reduce and its copy per iteration, the factors at the end */
+} irs_nmf_stats_t;
+irs_status irs_nmf_fit(int64_t n_users, int64_t n_items, const int64_t *indptr, const int32_t *indices,
+                       const float *data, int64_t k, float *W, float *H, float l1_W, float l2_W, float l1_H,
+                       float l2_H, double tol, int64_t max_iter, int32_t update_H, int32_t device, int64_t *n_iter,
+                       double *violations /* may be NULL */, irs_nmf_stats_t *stats /* may be NULL */);
+
 /* ------------------------------------------------------------ measurement
  * No reference counterpart: SURVEY.md 8(d) asks for ceilings MEASURED on the box next to the
  * spec peaks.  Runs a 1 GiB device copy and STREAM triad (HBM bytes moved / time), a loop of

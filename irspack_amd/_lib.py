@@ -112,6 +112,16 @@ class TruncSvdStatsStruct(C.Structure):  # irs_truncsvd_stats_t
     ]
 
 
+class NmfStatsStruct(C.Structure):  # irs_nmf_stats_t
+    _fields_ = [
+        ("setup_ms", C.c_double),
+        ("spmm_ms", C.c_double),
+        ("gram_ms", C.c_double),
+        ("sweep_ms", C.c_double),
+        ("d2h_ms", C.c_double),
+    ]
+
+
 ABI_VERSION = 4  # IRS_ABI_VERSION of include/irspack_amd.h
 # IRS_EXCHANGE_* of include/irspack_amd.h: how irs_ials_sharded_step moves the solved rows
 EXCHANGE_MODES = {"auto": 0, "broadcast": 1, "mesh": 2, "peer": 3}
@@ -183,6 +193,7 @@ EXPORTED_SYMBOLS = [
     "irs_truncsvd_finish",
     "irs_truncsvd_stats",
     "irs_truncsvd_destroy",
+    "irs_nmf_fit",
     "irs_eval_create",
     "irs_eval_destroy",
     "irs_eval_get_metrics",
@@ -218,6 +229,9 @@ ARGTYPES = {
     "irs_truncsvd_finish": [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float)],
     "irs_truncsvd_stats": [C.c_void_p, C.c_void_p],
     "irs_truncsvd_destroy": [C.c_void_p],
+    "irs_nmf_fit": [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int64,
+                    C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_float, C.c_double,
+                    C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_void_p],
 }
 
 _lib: Optional[C.CDLL] = None

@@ -7,6 +7,7 @@ from .edlae import EDLAERecommender
 from .ials import IALSRecommender
 from .knn import (AsymmetricCosineKNNRecommender, CosineKNNRecommender, JaccardKNNRecommender,
                   P3alphaRecommender, RP3betaRecommender, TverskyIndexKNNRecommender)
+from .nmf import NMFRecommender
 from .slim import SLIMRecommender
 from .truncsvd import TruncatedSVDRecommender
 from .user_knn import AsymmetricCosineUserKNNRecommender, CosineUserKNNRecommender
@@ -16,4 +17,4 @@ __all__ = ["BaseRecommender", "BaseSimilarityRecommender", "IALSRecommender",
            "TverskyIndexKNNRecommender", "P3alphaRecommender", "RP3betaRecommender",
            "BaseUserSimilarityRecommender", "CosineUserKNNRecommender",
            "AsymmetricCosineUserKNNRecommender", "SLIMRecommender", "DenseSLIMRecommender",
-           "EDLAERecommender", "TruncatedSVDRecommender"]
+           "EDLAERecommender", "TruncatedSVDRecommender", "NMFRecommender"]

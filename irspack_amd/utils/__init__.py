@@ -3,7 +3,8 @@
 (util.hpp:228-424, util.cpp:31-40); and the closed-form EASE / EDLAE weights (``dense_slim_weight``), which the
 reference computes with scipy inside ``recommenders/dense_slim.py`` and ``recommenders/edlae.py``; and the
 randomized truncated SVD (``truncated_svd``), which the reference takes from scikit-learn inside
-``recommenders/truncsvd.py``.
+``recommenders/truncsvd.py``; and the coordinate-descent NMF (``nmf_fit``, ``nmf_transform``), which the reference takes
+from scikit-learn inside ``recommenders/nmf.py``.
 
 Everything goes through the C ABI: ``remove_diagonal``, the serving top-k
 ``retrieve_recommend_from_score`` and the two feature weightings (``irs_knn_weight``; the kNN
@@ -11,6 +12,7 @@ recommenders do not call them - they hand the weighting to the computer's constr
 applies it on the device without a host copy of the weighted matrix).
 """
 
+import warnings
 from typing import List, Optional, Sequence, Tuple
 
 import ctypes as C
@@ -339,3 +341,185 @@ def truncated_svd(X, n_components: int, random_seed: int = 0, *, n_iter: int = 5
     finally:
         lib().irs_truncsvd_destroy(handle)
     return z, sigma, comps
+
+
+class ConvergenceWarning(UserWarning):
+    """scikit-learn's ``sklearn.exceptions.ConvergenceWarning`` by name (this package does not import scikit-learn)"""
+
+
+NMF_INITS = (None, "random", "nndsvd", "nndsvda", "nndsvdar")
+
+
+def nndsvd_init(U: np.ndarray, S: np.ndarray, Vt: np.ndarray, mean: float, variant: str = "nndsvda",
+                rng: Optional[np.random.RandomState] = None, eps: float = 1e-6) -> Tuple[np.ndarray, np.ndarray]:
+    """The NNDSVD arithmetic of scikit-learn's ``_initialize_nmf`` (Boutsidis & Gallopoulos 2008) on the host, in
+    the dtype of ``U``: from the singular triplets ``U (n, k)``, ``S (k,)``, ``Vt (k, m)`` to the non-negative
+    ``(W0 (n, k), H0 (k, m))``.  Every triplet past the first is split into its positive and negative parts and
+    the pair with the larger product of norms is kept, entries below ``eps`` become 0; ``variant``:
+    ``"nndsvd"`` leaves the zeros, ``"nndsvda"`` fills them with ``mean``, ``"nndsvdar"`` with
+    ``|mean * rng.standard_normal() / 100|`` (``W`` first).  The result does not depend on the sign of a triplet.
+    A triplet whose kept parts have norm 0 (a zero singular vector) gives a zero column and row, where
+    scikit-learn divides 0 by 0."""
+    if variant not in ("nndsvd", "nndsvda", "nndsvdar"):
+        raise ValueError(f"Invalid init parameter: got {variant!r} instead of one of {NMF_INITS!r}")
+    norm = lambda v: np.sqrt(np.dot(v, v))  # noqa: E731  (sklearn.utils.extmath.norm)
+    W, H = np.zeros_like(U), np.zeros_like(Vt)
+    W[:, 0] = np.sqrt(S[0]) * np.abs(U[:, 0])
+    H[0, :] = np.sqrt(S[0]) * np.abs(Vt[0, :])
+    for j in range(1, U.shape[1]):
+        x, y = U[:, j], Vt[j, :]
+        x_p, y_p = np.maximum(x, 0), np.maximum(y, 0)
+        x_n, y_n = np.abs(np.minimum(x, 0)), np.abs(np.minimum(y, 0))
+        x_p_nrm, y_p_nrm = norm(x_p), norm(y_p)
+        x_n_nrm, y_n_nrm = norm(x_n), norm(y_n)
+        m_p, m_n = x_p_nrm * y_p_nrm, x_n_nrm * y_n_nrm
+        if m_p > m_n:
+            u, v, sigma = x_p / x_p_nrm, y_p / y_p_nrm, m_p
+        elif m_n > 0:
+            u, v, sigma = x_n / x_n_nrm, y_n / y_n_nrm, m_n
+        else:
+            continue
+        lbd = np.sqrt(S[j] * sigma)
+        W[:, j] = lbd * u
+        H[j, :] = lbd * v
+    W[W < eps] = 0
+    H[H < eps] = 0
+    if variant == "nndsvda":
+        W[W == 0] = mean
+        H[H == 0] = mean
+    elif variant == "nndsvdar":
+        if rng is None:
+            raise ValueError("nndsvdar needs a random generator.")
+        W[W == 0] = abs(mean * rng.standard_normal(size=len(W[W == 0])) / 100)
+        H[H == 0] = abs(mean * rng.standard_normal(size=len(H[H == 0])) / 100)
+    return W, H
+
+
+def _nmf_matrix(X) -> sps.csr_matrix:
+    Xc = sps.csr_matrix(X, dtype=np.float32)
+    if not Xc.has_canonical_format:
+        Xc = Xc.copy()
+        Xc.sum_duplicates()  # (the C call rejects duplicate column indices within a row)
+    if Xc.nnz and Xc.data.min() < 0:
+        raise ValueError("Negative values in data passed to NMF (input X).")
+    return Xc
+
+
+def _nmf_call(Xc, W: np.ndarray, H: np.ndarray, alpha: float, l1_ratio: float, tol: float, max_iter: int,
+              update_H: bool, device: Optional[int], stats: Optional[dict]) -> int:
+    """``irs_nmf_fit`` on the float32 arrays ``W`` and ``H`` in place; sklearn's scaling of the regularisers
+    (``_compute_regularization`` with ``alpha_H = "same"``) and its convergence warning"""
+    n_users, n_items = Xc.shape
+    indptr = np.ascontiguousarray(Xc.indptr, dtype=np.int64)
+    indices = np.ascontiguousarray(Xc.indices, dtype=np.int32)
+    data = np.ascontiguousarray(Xc.data, dtype=np.float32)
+    if data.size == 0:
+        indices, data = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.float32)
+    n_iter = C.c_int64(0)
+    violations = np.zeros(max(int(max_iter), 1), dtype=np.float64)
+    st = _lib.NmfStatsStruct()
+    check(lib().irs_nmf_fit(
+        n_users, n_items, ptr(indptr, C.c_int64), ptr(indices, C.c_int32), ptr(data, C.c_float), W.shape[1],
+        ptr(W, C.c_float), ptr(H, C.c_float), n_items * alpha * l1_ratio, n_items * alpha * (1.0 - l1_ratio),
+        n_users * alpha * l1_ratio, n_users * alpha * (1.0 - l1_ratio), float(tol), int(max_iter),
+        1 if update_H else 0, _lib.default_device() if device is None else device, C.byref(n_iter),
+        ptr(violations, C.c_double), C.cast(C.byref(st), C.c_void_p) if stats is not None else None))
+    if stats is not None:
+        stats.update({name: getattr(st, name) for name, _ in _lib.NmfStatsStruct._fields_},
+                     violations=violations[:n_iter.value].copy())
+    if n_iter.value == max_iter and tol > 0:
+        warnings.warn("Maximum number of iterations %d reached. Increase it to improve convergence." % max_iter,
+                      ConvergenceWarning)
+    return int(n_iter.value)
+
+
+def _check_nmf_params(alpha: float, l1_ratio: float, tol: float, max_iter: int) -> None:
+    if not alpha >= 0:
+        raise ValueError("alpha must be >= 0.")
+    if not 0 <= l1_ratio <= 1:
+        raise ValueError("l1_ratio must be in [0, 1].")
+    if not tol >= 0:
+        raise ValueError("tol must be >= 0.")
+    if max_iter < 1:
+        raise ValueError("max_iter must be >= 1.")
+
+
+def nmf_fit(X, n_components: int, alpha: float = 0.0, l1_ratio: float = 0.0, *, init: Optional[str] = None,
+            random_state: int = 42, tol: float = 1e-4, max_iter: int = 200, W0: Optional[np.ndarray] = None,
+            H0: Optional[np.ndarray] = None, device: Optional[int] = None, stats: Optional[dict] = None):
+    """The fit of ``sklearn.decomposition.NMF(n_components, init=init, solver="cd", beta_loss="frobenius",
+    alpha_W=alpha, alpha_H="same", l1_ratio=l1_ratio, random_state=random_state, tol=tol, max_iter=max_iter)``
+    (what nmf.py:48-64 of the reference fits) on the device (``irs_nmf_fit``), float32: alternating exact
+    Gauss-Seidel coordinate sweeps over the rows of ``W`` and the columns of ``H``, coordinates ascending,
+    stopped by sklearn's projected-gradient test.  Returns ``(W (U, k), H (k, I), n_iter)``, the factors float32
+    and C-contiguous.  Two calls give identical bytes.  Duplicate entries of ``X`` are summed first.
+
+    ``init``: ``None`` is ``"nndsvda"`` when ``n_components <= min(X.shape)``, else ``"random"``;
+    ``"random"`` is sklearn's draw (``H`` first); the NNDSVD variants (:func:`nndsvd_init`) start from
+    :func:`truncated_svd` with sklearn's automatic iteration count (7 when ``n_components < 0.1 min(X.shape)``,
+    else 4) - the float32 device SVD in the place of sklearn's float64 one, so the start differs from sklearn's
+    by rounding.  ``W0`` and ``H0`` (both or neither) are sklearn's ``init="custom"``.  An all-zero ``X`` without
+    custom factors gives zero factors and ``n_iter = 1``, as sklearn does.
+
+    When ``max_iter`` is reached and ``tol > 0``, sklearn's ``ConvergenceWarning`` is raised (a ``UserWarning``
+    subclass of that name).  ``stats`` receives the device phase times ``setup_ms, spmm_ms, gram_ms, sweep_ms,
+    d2h_ms`` (HIP events) and ``violations``, the per-iteration violation sums."""
+    Xc = _nmf_matrix(X)
+    n_users, n_items = Xc.shape
+    k = int(n_components)
+    if k < 1:
+        raise ValueError("n_components must be >= 1.")
+    _check_nmf_params(alpha, l1_ratio, tol, max_iter)
+    if (W0 is None) != (H0 is None):
+        raise ValueError("W0 and H0 go together: both or neither.")
+    if init not in NMF_INITS:
+        raise ValueError(f"Invalid init parameter: got {init!r} instead of one of {NMF_INITS!r}")
+    if init not in (None, "random") and W0 is None and k > min(n_users, n_items):
+        raise ValueError(f"init = '{init}' can only be used when n_components <= min(n_samples, n_features)")
+    if n_users == 0 or n_items == 0:
+        raise ValueError("the matrix must have at least one row and one column.")
+    if W0 is not None:
+        W = np.array(W0, dtype=np.float32, order="C")
+        H = np.array(H0, dtype=np.float32, order="C")
+        if W.shape != (n_users, k) or H.shape != (k, n_items):
+            raise ValueError(f"W0 must be {(n_users, k)} and H0 {(k, n_items)}.")
+    elif not Xc.data.any():
+        if stats is not None:
+            stats.update({name: 0.0 for name, _ in _lib.NmfStatsStruct._fields_}, violations=np.zeros(1))
+        return np.zeros((n_users, k), dtype=np.float32), np.zeros((k, n_items), dtype=np.float32), 1
+    else:
+        mean = float(Xc.data.sum(dtype=np.float64)) / (float(n_users) * float(n_items))
+        if init is None:
+            init = "nndsvda" if k <= min(n_users, n_items) else "random"
+        if init == "random":
+            avg = np.sqrt(mean / k)
+            rng = np.random.RandomState(random_state)
+            H64 = np.abs(avg * rng.standard_normal(size=(k, n_items)))
+            W64 = np.abs(avg * rng.standard_normal(size=(n_users, k)))
+        else:
+            auto_iter = 7 if k < 0.1 * min(n_users, n_items) else 4
+            z, sigma, comps = truncated_svd(Xc, k, random_state, n_iter=auto_iter, device=device)
+            S = sigma.astype(np.float64)
+            U = np.where(S > 0, z.astype(np.float64) / np.where(S > 0, S, 1.0), 0.0)
+            W64, H64 = nndsvd_init(U, S, comps.astype(np.float64), mean, init, np.random.RandomState(random_state))
+        W = np.ascontiguousarray(W64, dtype=np.float32)
+        H = np.ascontiguousarray(H64, dtype=np.float32)
+    n_iter = _nmf_call(Xc, W, H, float(alpha), float(l1_ratio), float(tol), int(max_iter), True, device, stats)
+    return W, H, n_iter
+
+
+def nmf_transform(X, H: np.ndarray, alpha: float = 0.0, l1_ratio: float = 0.0, *, tol: float = 1e-4,
+                  max_iter: int = 200, device: Optional[int] = None, stats: Optional[dict] = None) -> np.ndarray:
+    """``NMF.transform`` of a model with ``components_ = H`` (what ``get_score_cold_user`` of the reference calls):
+    the same loop with ``H`` fixed and only ``W`` swept, from ``W = 0`` as scikit-learn 1.x starts its ``cd``
+    solver there, the regularisers scaled by the shape of ``X``.  Returns ``W (rows of X, k)`` float32."""
+    Xc = _nmf_matrix(X)
+    Hc = np.array(H, dtype=np.float32, order="C")
+    if Hc.ndim != 2 or Hc.shape[1] != Xc.shape[1]:
+        raise ValueError(f"H must be (k, {Xc.shape[1]}).")
+    _check_nmf_params(alpha, l1_ratio, tol, max_iter)
+    W = np.zeros((Xc.shape[0], Hc.shape[0]), dtype=np.float32)
+    if Xc.shape[0] == 0:
+        return W
+    _nmf_call(Xc, W, Hc, float(alpha), float(l1_ratio), float(tol), int(max_iter), False, device, stats)
+    return W
