@@ -12,6 +12,7 @@ namespace nmf {
 
 constexpr int SWEEP_ROWS = 64;  // rows of a workgroup: one wave, one lane per row
 constexpr int SWEEP_CB = 16;    // coordinates resolved together
+constexpr int SWEEP_CHUNK = 64; // coordinates of a dot product added in one chain (a multiple of SWEEP_CB)
 
 // G[t, t] += l2 for t < k: the tiny prologue of a sweep (the padded diagonal stays zero)
 static __global__ __launch_bounds__(64) void nmf_ridge_kernel(float *__restrict__ G, int k, int ld, float l2) {
@@ -27,7 +28,9 @@ static __global__ __launch_bounds__(64) void nmf_ridge_kernel(float *__restrict_
 // reads the lane's own row of W (a float4 at a time; blocks before this one hold this sweep's values already,
 // written by this same lane) against G[r, t_0 .. t_0 + 15] - G is symmetric to the bit, so row r holds the 16
 // factors side by side, and the address is the same in every lane: a uniform load of 16 values per 16 fused
-// multiply-adds on 64 rows.  The block itself is resolved against its 16 x 16 diagonal block of G with the 16
+// multiply-adds on 64 rows.  The r loop goes in chunks of SWEEP_CHUNK coordinates, each summed from zero and then
+// added to g: one chain over all k terms is, at k = 257, four times as far from float64 as a BLAS dot product
+// is (which adds in blocks too), the chunked sum no farther.  The block itself is resolved against its 16 x 16 diagonal block of G with the 16
 // values of W in registers.  The violation is added per row in coordinate order in double, the rows of the
 // workgroup in ascending order by lane 0, to partial[blockIdx.x].
 static __global__ __launch_bounds__(SWEEP_ROWS) void nmf_sweep_kernel(float *W, const float *__restrict__ XH,
@@ -52,16 +55,24 @@ static __global__ __launch_bounds__(SWEEP_ROWS) void nmf_sweep_kernel(float *W, 
       g[4 * q + 0] = -(x.x - l1), g[4 * q + 1] = -(x.y - l1), g[4 * q + 2] = -(x.z - l1), g[4 * q + 3] = -(x.w - l1);
       w[4 * q + 0] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
     }
-    for (int r0 = 0; r0 < k4; r0 += 4) {
-      if (r0 >= t0 && r0 < t0 + SWEEP_CB) continue;  // (uniform: the block's own coordinates come below)
-      const float4 v = *reinterpret_cast<const float4 *>(w_row + r0);
-      const float vv[4] = {v.x, v.y, v.z, v.w};
+    for (int c0 = 0; c0 < k4; c0 += SWEEP_CHUNK) {
+      const int c1 = min(k4, c0 + SWEEP_CHUNK);
+      float h[SWEEP_CB];
 #pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const float *g_row = G + static_cast<size_t>(r0 + u) * ld + t0;
+      for (int j = 0; j < SWEEP_CB; j++) h[j] = 0.f;
+      for (int r0 = c0; r0 < c1; r0 += 4) {
+        if (r0 >= t0 && r0 < t0 + SWEEP_CB) continue;  // (uniform: the block's own coordinates come below)
+        const float4 v = *reinterpret_cast<const float4 *>(w_row + r0);
+        const float vv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-        for (int j = 0; j < SWEEP_CB; j++) g[j] = fmaf(g_row[j], vv[u], g[j]);
+        for (int u = 0; u < 4; u++) {
+          const float *g_row = G + static_cast<size_t>(r0 + u) * ld + t0;
+#pragma unroll
+          for (int j = 0; j < SWEEP_CB; j++) h[j] = fmaf(g_row[j], vv[u], h[j]);
+        }
       }
+#pragma unroll
+      for (int j = 0; j < SWEEP_CB; j++) g[j] += h[j];
     }
 #pragma unroll
     for (int j = 0; j < SWEEP_CB; j++) {

@@ -7,7 +7,12 @@ restatement in float32, ``R32``, start from the same float32 ``W0 / H0`` (scikit
 scikit-learn is there, else the restatement's ``random`` init) and run ``max_iter`` iterations with ``tol = 0``.
 The bar of a case is measured, not fixed: the GPU may be at most 4 x as far from ``R64`` as ``R32`` is, with a
 floor of 4 x 2^-24 x the largest magnitude of the compared array and a cap of 1e-4 of it (a case that takes the
-cap says so in its parity line).  Compared: ``W @ H``, ``W`` and ``H``, max abs difference each."""
+cap says so in its parity line).  Compared: ``W @ H``, ``W`` and ``H``, max abs difference each, and the violation
+sum of every iteration, relative to ``R64``'s (``violation_bars``).
+
+The probes of section 8 need no bar: with one non-zero per column of ``H`` and small integers in ``X`` every
+sum of one transform step is exact in float32, and the GPU is compared for equality."""
+import contextlib
 import pickle
 import time
 import warnings
@@ -72,24 +77,58 @@ def check_factors(X, k, W, H):
         assert a.dtype == np.float32 and a.flags.c_contiguous and np.isfinite(a).all() and (a >= 0).all()
 
 
-def compare(test, config, X, k, alpha=1e-2, l1_ratio=1e-2, max_iter=3, init=None):
+def one_blas_thread():
+    """The restatement sweeps one coordinate at a time, a matrix-vector product each (3,120 of them on 3,000 x 520
+    at k = 520): a threaded BLAS spends several times the product itself on handing it out.  Where threadpoolctl
+    is installed the restatement runs on one thread, which is also the order of sums closest to the Cython loop;
+    BLAS does not thread the products of the smaller cases, whose references are the same bytes either way."""
+    try:
+        from threadpoolctl import threadpool_limits
+    except ImportError:
+        return contextlib.nullcontext()
+    return threadpool_limits(limits=1, user_api="blas")
+
+
+def violation_bars(h32, h64):
+    """per iteration: 4 x the relative distance of ``R32``'s violation sum from ``R64``'s, with a floor of
+    16 x 2^-24 (``R32`` is sometimes exact by accident; the sum is one-signed over k-term float32 dot products,
+    hence 16 where the factors have 4) and the 1e-4 cap"""
+    return np.maximum(np.minimum(4.0 * np.abs(h32 / h64 - 1.0), 1e-4), 16.0 * EPS)
+
+
+def compare(test, config, X, k, alpha=1e-2, l1_ratio=1e-2, max_iter=3, init=None, uncapped=False):
+    """``uncapped``: the case is there for its measured bar, so ``R32`` taking the 1e-4 cap on any compared array
+    fails it (a precondition on the CPU side: change the matrix, not the bar)"""
     W0, H0 = start(X, k, init)
     stats = {}
     W, H, n_iter = nmf_fit(X, k, alpha, l1_ratio, tol=0.0, max_iter=max_iter, W0=W0, H0=H0, stats=stats)
     check_factors(X, k, W, H)
     assert n_iter == max_iter and stats["violations"].shape == (max_iter,)
-    W64, H64, _, h64 = nmf_cd(X, W0, H0, alpha, l1_ratio, 0.0, max_iter, np.float64)
-    W32, H32, _, _ = nmf_cd(X, W0, H0, alpha, l1_ratio, 0.0, max_iter, np.float32)
-    fields, failures = {}, []
+    with one_blas_thread():
+        W64, H64, _, h64 = nmf_cd(X, W0, H0, alpha, l1_ratio, 0.0, max_iter, np.float64)
+        W32, H32, _, h32 = nmf_cd(X, W0, H0, alpha, l1_ratio, 0.0, max_iter, np.float32)
+    fields, failures, cap_taken = {}, [], []
     for name, (e_gpu, top), (e_r32, _) in zip(("WH", "W", "H"), factor_errors(W, H, W64, H64),
                                               factor_errors(W32, H32, W64, H64)):
         bar, capped = bar_of(e_r32, top)
         fields.update({f"{name}_err_gpu": e_gpu, f"{name}_err_r32": e_r32, f"{name}_bar": bar, f"{name}_max": top,
                        f"{name}_bar_is_the_1e-4_cap": capped})
+        if capped:
+            cap_taken.append((name, e_r32, top))
         if not e_gpu <= bar:
             failures.append((name, e_gpu, e_r32, bar))
-    fields["violation_rel_err"] = float(np.abs(stats["violations"] / h64 - 1.0).max()) if (h64 > 0).all() else None
+    fields.update(violation_rel_err=None, violation_rel_err_r32=None, violation_bar=None)
+    if (h64 > 0).all():  # (else there is no relative distance: recorded as null, not asserted)
+        v_gpu, v_r32, v_bar = np.abs(stats["violations"] / h64 - 1.0), np.abs(h32 / h64 - 1.0), violation_bars(h32, h64)
+        fields.update(violation_rel_err=float(v_gpu.max()), violation_rel_err_r32=float(v_r32.max()),
+                      violation_bar=float(v_bar.min()), violation_rel_err_by_iteration=[float(v) for v in v_gpu],
+                      violation_rel_err_r32_by_iteration=[float(v) for v in v_r32],
+                      violation_bar_by_iteration=[float(v) for v in v_bar])
+        for it in np.flatnonzero(~(v_gpu <= v_bar)):
+            failures.append((f"violation of iteration {it + 1}", float(v_gpu[it]), float(v_r32[it]), float(v_bar[it])))
     record_parity(test, config, **fields)
+    if uncapped:
+        assert not cap_taken, cap_taken
     assert not failures, failures
     return W, H
 
@@ -118,6 +157,47 @@ def test_row_longer_than_a_product_segment():
     assert X[0].nnz > 1024 and X.shape[0] < X.shape[1]
     compare("test_row_longer_than_a_product_segment", "40 x 1500, 1300 in row 0, k=8", X, 8)
     compare("test_row_longer_than_a_product_segment", "its transpose, k=8", sps.csr_matrix(X.T), 8)
+
+
+@pytest.mark.parametrize("k", [256, 257, 320, 512, 513, 576])
+def test_matches_float64_restatement_at_wide_k(k):
+    """k_pad = 256 is the widest one-chunk product (every lane on); 320 (k = 257, 320) and 512 are the two-chunk
+    one with the second chunk partly masked and full; 576 (k = 513, 576) is the three-chunk one.  257 and 513
+    leave k % 16 = k % 4 = 1 to the sweep.  k > min(shape): the random start"""
+    compare("test_matches_float64_restatement_at_wide_k", f"300 x 200 k={k}", base_matrix(), k)
+
+
+@pytest.mark.parametrize("shape", [(20000, 64), (64, 20000)])
+def test_tall_block_at_k3(shape):
+    """20,000 rows at k_pad = 64: the Gram pass of that side has 313 chunks of 64 rows for 256 slabs at most, so
+    157 slabs of two chunks - the second pass of the kernel's row loop - of which the last has one chunk, and
+    that chunk 32 rows; its sweep leaves 313 partial violations, more than the 256 threads that add them"""
+    X = random_csr(shape[0], shape[1], 0.05, 4)
+    compare("test_tall_block_at_k3", f"{shape[0]} x {shape[1]} k=3", X, 3)
+
+
+def test_gram_slabs_of_two_chunks_with_off_diagonal_tiles():
+    """k = 520, k_pad = 576: 45 tiles, so 2048 // 45 = 45 slabs at most for the 47 chunks of 3,000 rows: 24 slabs
+    of two chunks, the last with one chunk of 56 rows"""
+    X = random_csr(3000, 80, 0.05, 6)
+    compare("test_gram_slabs_of_two_chunks_with_off_diagonal_tiles", "3000 x 80 k=520", X, 520, uncapped=True)
+
+
+def test_split_rows_on_both_sides():
+    """two rows and two columns longer than a product segment: X and X^T have two split rows each (the second
+    one's partial slots do not start at 0), and one buffer of partial rows serves both products"""
+    def make():
+        X = random_csr(1500, 1500, 0.01, 7).tolil()
+        rng = np.random.default_rng(13)
+        for r, n in ((0, 1300), (2, 1100)):
+            X[r, np.sort(rng.choice(1500, size=n, replace=False))] = rng.uniform(0.5, 3.0, size=n)
+        for c, n in ((1, 1200), (4, 1400)):
+            X[np.sort(rng.choice(1500, size=n, replace=False)), c] = rng.uniform(0.5, 3.0, size=n)
+        return sps.csr_matrix(X.tocsr(), dtype=np.float32)
+    X = cached("split_both", make)
+    for M in (X, sps.csr_matrix(X.T)):
+        assert (np.diff(M.indptr) > 1024).sum() == 2 and np.diff(M.indptr).max() <= 2048
+    compare("test_split_rows_on_both_sides", "1500 x 1500, rows 0, 2 and columns 1, 4 split, k=8", X, 8)
 
 
 def test_binary_matrix():
@@ -292,3 +372,79 @@ def test_ml20m_shape_k64():
     assert np.isfinite(violations).all()
     record_parity("test_ml20m_shape_k64", f"{X.shape[0]} x {X.shape[1]}, nnz={X.nnz}", generate_s=t1 - t0,
                   fit_wall_s=t2 - t1, violations=[float(v) for v in violations], **stats)
+
+
+# ------------------------------------------------------------------ 8. exact probes of one transform step
+def probe_components(k):
+    """``H`` (k x (4 k + 5)) with one non-zero per column: item j < 4 k belongs to component j % k, 1.0 in an even
+    component and 2.0 in an odd one; the last five items are zero columns.  ``H H^T`` is diagonal, 4 and 16"""
+    n_items = 4 * k + 5
+    H = np.zeros((k, n_items), dtype=np.float32)
+    j = np.arange(4 * k)
+    H[j % k, j] = np.where((j % k) % 2 == 0, 1.0, 2.0)
+    return H
+
+
+def probe_matrix(n_rows, n_items, seed, long_rows=()):
+    """5 % dense with integer values 1 .. 5; ``long_rows``: (row, number of entries) to overwrite"""
+    rng = np.random.default_rng(seed)
+    X = random_csr(n_rows, n_items, 0.05, seed).tolil()
+    for r, n in long_rows:
+        cols = np.sort(rng.choice(n_items, size=n, replace=False))
+        X.rows[r], X.data[r] = cols.tolist(), [1.0] * n
+    X = sps.csr_matrix(X.tocsr(), dtype=np.float32)
+    X.data = rng.integers(1, 6, size=X.nnz).astype(np.float32)
+    return X
+
+
+def exact_probe(test, config, X, k):
+    """One transform step (a product, a Gram pass, a sweep from ``W = 0``) on sums that are exact in float32:
+    ``W[i, t] == XH[i, t] / G[t, t]`` and the violation is the sum of ``XH``, as a double, whatever the order"""
+    H = probe_components(k)
+    X64, H64 = sps.csr_matrix(X, dtype=np.float64), H.astype(np.float64)
+    XH, G = np.asarray(X64 @ H64.T), H64 @ H64.T
+    diag = np.diag(G)
+    want = XH / diag
+    # the preconditions of "exact": integer sums a float32 holds, a diagonal G, a division without rounding
+    assert XH.max() < 2 ** 24 and (XH == np.rint(XH)).all() and XH.any()
+    assert not (G - np.diag(diag)).any() and set(diag) <= {4.0, 16.0}
+    assert (want * diag == XH).all() and (want.astype(np.float32) == want).all()
+    r64, _, h64 = restated_transform(X, H, 0.0, 0.0, 0.0, 1, np.float64)
+    assert np.array_equal(r64, want) and h64[0] == XH.sum()
+    stats = {}
+    W = nmf_transform(X, H, 0.0, 0.0, tol=0.0, max_iter=1, stats=stats)
+    assert W.shape == want.shape and W.dtype == np.float32 and stats["violations"].shape == (1,)
+    violation = float(stats["violations"][0])
+    exact = bool(np.array_equal(W, want) and (W >= 0).all() and violation == XH.sum())
+    record_parity(test, config, exact=exact, XH_max=float(XH.max()), violation=violation,
+                  violation_expected=float(XH.sum()), n_mismatches=int((W != want).sum()))
+    if not np.array_equal(W, want):
+        i, t = (int(v) for v in np.argwhere(W != want)[0])
+        print(f"first mismatch at (i, t) = ({i}, {t}): got {W[i, t]!r}, expected {want[i, t]!r}; XH = {XH[i, t]!r}, "
+              f"G[t, t] = {diag[t]!r}, entries in row i = {X[i].nnz}")
+    assert np.array_equal(W, want)
+    assert (W >= 0).all()
+    assert violation == XH.sum(), (violation, XH.sum())
+    return W
+
+
+@pytest.mark.parametrize("k", [1, 17, 64, 65, 256, 257, 320, 512, 513, 576])
+def test_one_transform_step_is_exact(k):
+    """every instantiation of the product (k_pad 64, 128, 256, 320, 512, 576: lanes per row 16, 32, 64 and two
+    and three chunks a lane) and a sweep with and without a coordinate tail.  At k = 576 row 0 has 2,100 entries
+    (three segments) and row 5 has 1,100 (two segments whose partial slots start at 3)"""
+    n_items = 4 * k + 5
+    long_rows = ((0, 2100), (5, 1100)) if k == 576 else ()
+    X = probe_matrix(70, n_items, 100 + k, long_rows)
+    if long_rows:
+        assert X[0].nnz == 2100 and X[5].nnz == 1100
+    exact_probe("test_one_transform_step_is_exact", f"70 x {n_items} k={k}", X, k)
+
+
+def test_violation_total_over_313_workgroups_is_exact():
+    """20,000 rows: the sweep leaves 313 partial sums for 256 adding threads, so the first 57 threads take a
+    second one; the total of integers does not depend on the order"""
+    t0 = time.perf_counter()
+    X = probe_matrix(20000, 17, 3)
+    assert time.perf_counter() - t0 < 1.0
+    exact_probe("test_violation_total_over_313_workgroups_is_exact", "20000 x 17 k=3", X, 3)

@@ -17,7 +17,7 @@ import pytest
 import scipy.sparse as sps
 
 from _truncsvd_restatement import randomized_truncated_svd, score_error, sigma_error
-from conftest import record_parity
+from conftest import random_csr, record_parity
 from irspack_amd.synthetic import holdout_split, make_interactions
 from irspack_amd.utils import truncated_svd
 
@@ -50,7 +50,9 @@ def check_outputs(X, k, z, s, c):
     return live
 
 
-def compare(test, config, X, k, seed=0, full_rank=True, **kw):
+def compare(test, config, X, k, seed=0, full_rank=True, uncapped=False, **kw):
+    """``uncapped``: the case is there for its measured bar, so ``R32`` taking the 1e-4 cap fails it (a
+    precondition on the CPU side: change the case, not the bar)"""
     z, s, c = truncated_svd(X, k, seed, **kw)
     live = check_outputs(X, k, z, s, c)
     z64, s64, c64 = randomized_truncated_svd(X, k, seed, np.float64, **kw)
@@ -65,6 +67,8 @@ def compare(test, config, X, k, seed=0, full_rank=True, **kw):
     record_parity(test, config, n_live=int(live.sum()), score_err_gpu=e_gpu, score_err_r32=e_r32, score_bar=bar,
                   score_ratio=e_gpu / max(e_r32, 1e-300), score_max=top, sigma_err_gpu=g_gpu, sigma_err_r32=g_r32,
                   sigma_bar=sbar, sigma_ratio=g_gpu / max(g_r32, 1e-300), ortho=ortho)
+    if uncapped:
+        assert 4.0 * e_r32 <= 1e-4 * top and 4.0 * g_r32 <= 1e-4, (e_r32, top, g_r32)
     assert e_gpu <= bar, (e_gpu, e_r32, bar)
     assert g_gpu <= sbar, (g_gpu, g_r32, sbar)
     assert ortho <= 1e-5, ortho
@@ -95,6 +99,29 @@ def test_fewer_power_iterations(n_iter):
 
 def test_no_oversampling():
     compare("test_no_oversampling", "n_oversamples=0 k=64", ml100k(), 64, n_oversamples=0)
+
+
+def wide_matrix():
+    if "wide" not in _CACHE:
+        _CACHE["wide"] = random_csr(700, 600, 0.1, 2)
+    return _CACHE["wide"]
+
+
+@pytest.mark.parametrize("k", [300, 500])
+def test_two_chunk_sketch_width(k):
+    """l = k + 10 = 310 and 510, l_pad = 320 and 512: a lane of the sparse product holds two float4 of a row, the
+    second one masked past lane 15 at 320 and on every lane at 512 (ML-100K at k = 256 would reach 320 too, but
+    there R32 itself is 2.3e-4 from R64 and the bar would be the cap)"""
+    compare("test_two_chunk_sketch_width", f"700 x 600 k={k}", wide_matrix(), k, uncapped=True)
+
+
+@pytest.mark.parametrize("shape", [(20000, 64), (64, 20000)])
+def test_tall_block_at_k4(shape):
+    """20,000 rows at l_pad = 64: the Gram pass over that side has 313 chunks of 64 rows for 256 slabs at most,
+    so 157 slabs of two chunks - the second pass of the kernel's row loop - of which the last has one chunk, and
+    that chunk 32 rows.  The transpose puts the 20,000 rows on the other side's Gram and apply"""
+    X = random_csr(shape[0], shape[1], 0.05, 4)
+    compare("test_tall_block_at_k4", f"{shape[0]} x {shape[1]} k=4", X, 4)
 
 
 # ------------------------------------------------------------------ 2. rank deficiency
