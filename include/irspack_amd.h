@@ -434,6 +434,34 @@ irs_status irs_eval_get_metrics_similarity(irs_evaluator *e, int64_t begin, int6
                                            const int64_t *cutoffs, int64_t offset,
                                            int32_t recall_with_cutoff, irs_metrics *out,
                                            int64_t *item_cnt);
+/* The same for a similarity model whose weights are a DENSE array (DenseSLIM / EASE, EDLAE): x_* are the
+ * profiles X [n_model_users, n_profile_cols] as CSR float64, read in their STORAGE order (the rows need not be
+ * sorted and are not copied into another order), w is W [n_profile_cols, n_items] row-major, float32
+ * (w_is_f64 == 0) or float64, uploaded once per call and not kept.  Per (user, column) the score is the chain
+ * acc = acc + x * (double)w over the user's stored entries, product and sum rounded separately: scipy's
+ * `X[b:e].dot(W)` (csr_matvecs) bit for bit.  Mask, cutoffs, offset and outputs as in
+ * irs_eval_get_metrics_similarity. */
+irs_status irs_eval_get_metrics_dense_similarity(irs_evaluator *e, int64_t begin, int64_t end,
+                                                 int64_t n_model_users, int64_t n_profile_cols,
+                                                 const int64_t *x_indptr, const int32_t *x_indices,
+                                                 const double *x_data, int32_t w_is_f64, const void *w,
+                                                 const int64_t *mask_indptr, const int32_t *mask_indices,
+                                                 int32_t n_cutoffs, const int64_t *cutoffs, int64_t offset,
+                                                 int32_t recall_with_cutoff, irs_metrics *out,
+                                                 int64_t *item_cnt);
+/* The same for a FACTOR model (truncated SVD, NMF): score = user_factors[u] @ item_factors^T in float32
+ * through the fp32 MFMA tiles of the iALS scores (operands zero-padded to a multiple of 32 on upload), for the
+ * users begin .. end of user_factors [n_model_users, k] against item_factors [n_items, k], both host
+ * row-major, 1 <= k <= 576; masked and ranked once per cutoff as above. */
+irs_status irs_eval_get_metrics_factors(irs_evaluator *e, int64_t begin, int64_t end,
+                                        int64_t n_model_users, int32_t k, const float *user_factors,
+                                        const float *item_factors, const int64_t *mask_indptr,
+                                        const int32_t *mask_indices, int32_t n_cutoffs,
+                                        const int64_t *cutoffs, int64_t offset,
+                                        int32_t recall_with_cutoff, irs_metrics *out, int64_t *item_cnt);
+/* Stream time of the last irs_eval_get_metrics_dense_similarity / _factors call by phase, in milliseconds
+ * (measurement only): ms[0] uploads, ms[1] scoring, ms[2] masking, ms[3] ranking and folding. */
+irs_status irs_eval_last_phases(irs_evaluator *e, double *ms);
 /* Fused device path used by the Evaluator counterpart when the model is an
  * iALS trainer of this library: scores = user[begin:end] @ item^T (hpp:942-984)
  * are produced, masked (evaluator.py:417-432, mask = CSR rows given here, set

@@ -199,6 +199,9 @@ EXPORTED_SYMBOLS = [
     "irs_eval_get_metrics",
     "irs_eval_get_metrics_masked",
     "irs_eval_get_metrics_similarity",
+    "irs_eval_get_metrics_dense_similarity",
+    "irs_eval_get_metrics_factors",
+    "irs_eval_last_phases",
     "irs_eval_get_metrics_ials",
     "irs_eval_cache_mask",
     "irs_eval_last_stats",
@@ -232,6 +235,15 @@ ARGTYPES = {
     "irs_nmf_fit": [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int64,
                     C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_float, C.c_double,
                     C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_void_p],
+    "irs_eval_get_metrics_dense_similarity": [
+        C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+        C.POINTER(C.c_double), C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32,
+        C.POINTER(C.c_int64), C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)],
+    "irs_eval_get_metrics_factors": [
+        C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+        C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int64), C.c_int64, C.c_int32,
+        C.c_void_p, C.POINTER(C.c_int64)],
+    "irs_eval_last_phases": [C.c_void_p, C.POINTER(C.c_double)],
 }
 
 _lib: Optional[C.CDLL] = None

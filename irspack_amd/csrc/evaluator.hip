@@ -1018,6 +1018,32 @@ __global__ void reduce_partials_kernel(const RowPartial *partials, int nb, int64
   out->map += acc[4];
 }
 
+// Rows per block of the Evaluator's host loop (`mb_size`, evaluator.py:363-367: 128 by default).  A call that
+// scores a model's users on the device adds their terms as that loop does - per chunk of this many rows the
+// sum of reduce_rows_kernel (what a 128-row block call returns), then Metrics::merge chunk after chunk onto the
+// running totals (evaluator.cpp:76-85) - so its float64 sums are the default loop's to the last bit.
+constexpr int64_t HOST_LOOP_ROWS = 128;
+__global__ void merge_partials_kernel(const RowPartial *partials, int nb, int64_t n, irs_metrics *out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  long long v = out->valid_user;
+  double acc[5] = {out->hit, out->recall, out->ndcg, out->precision, out->map};
+  for (int b = 0; b < nb; b++) {  // chunk order, every chunk onto the running sum
+    v += partials[b].valid;
+    acc[0] += partials[b].hit;
+    acc[1] += partials[b].recall;
+    acc[2] += partials[b].ndcg;
+    acc[3] += partials[b].precision;
+    acc[4] += partials[b].map;
+  }
+  out->valid_user = v;
+  out->total_user += n;
+  out->hit = acc[0];
+  out->recall = acc[1];
+  out->ndcg = acc[2];
+  out->precision = acc[3];
+  out->map = acc[4];
+}
+
 // item_cnt[i] += how often item i stands in the recommended lists of a call (Metrics::update,
 // evaluator.cpp:146).  `rec` = the lists the ranking kernels wrote ([rows, cutoff], -1 where
 // there is no entry).  Everybody's list is full of the same popular items, so one global atomic
@@ -1247,10 +1273,15 @@ __global__ __launch_bounds__(64) void sim_score_kernel(const int64_t *__restrict
 
 }  // namespace eval
 }  // namespace irs
+#include "eval_dense_kernels.hpp"
 
 using namespace irs;
 using namespace irs::eval;
 
+// exported by ials.hip: user[0:m] @ item^T of factor tables the CALLER holds on the device ([rows, KP]
+// row-major, KP a multiple of 32, padded columns zero) through the fp32 MFMA tiles of the iALS scores
+extern "C" irs_status irs_gk_scores_device_(const float *user, const float *item, int32_t KP, int64_t m,
+                                            int64_t n_items, float *device_out, void *stream);
 // exported by ials.hip for the fused path
 extern "C" irs_status irs_ials_scores_device_(irs_ials_trainer *t, int64_t begin, int64_t end,
                                               float *device_out, void **stream_out,
@@ -1298,6 +1329,7 @@ struct irs_evaluator {
   irs_eval_stats stats{};  // of the last irs_eval_get_metrics_ials call
   hipEvent_t ev_first = nullptr, ev_last = nullptr;  // span of that call's device work
   bool span_open = false;
+  double phase_ms[4] = {0.0, 0.0, 0.0, 0.0};  // of the last dense-similarity / factor-model call (irs_eval_last_phases)
 };
 
 namespace {
@@ -1386,9 +1418,11 @@ template <class T> void launch_rank(EvalParams p, int64_t max_cand, hipStream_t 
 }
 
 // ranks `rows` rows already resident at `d_scores` and accumulates into out / item_cnt
+// (`running`, when given: the per-user terms are added to `running` in HOST_LOOP_ROWS-row chunks, chunk after
+// chunk, instead of to e->metrics - see CutoffTotals)
 template <class T>
 void rank_block(irs_evaluator *e, const void *d_scores, int64_t rows, int64_t cutoff,
-                int64_t offset, bool rwc, hipStream_t s) {
+                int64_t offset, bool rwc, hipStream_t s, irs_metrics *running = nullptr) {
   e->row_out.alloc(rows);
   e->rec_out.alloc(rows * cutoff);
   e->todo.alloc(rows);
@@ -1412,8 +1446,17 @@ void rank_block(irs_evaluator *e, const void *d_scores, int64_t rows, int64_t cu
   p.item_cnt = e->item_cnt.ptr;
   launch_rank<T>(p, e->n_items, s, e->todo.ptr);
   launch_item_hist(e->rec_out.ptr, rows * cutoff, e->item_cnt.ptr, s, e->n_items);
-  hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(1024), 0, s, e->row_out.ptr, rows,
-                     e->metrics.ptr);
+  if (running) {
+    const int nb = static_cast<int>(ceil_div(rows, HOST_LOOP_ROWS));
+    e->row_partials.alloc(nb);
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(nb), dim3(1024), 0, s, e->row_out.ptr, rows, running,
+                       e->row_partials.ptr, HOST_LOOP_ROWS);
+    hipLaunchKernelGGL(merge_partials_kernel, dim3(1), dim3(64), 0, s,
+                       static_cast<const RowPartial *>(e->row_partials.ptr), nb, rows, running);
+  } else {
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(1024), 0, s, e->row_out.ptr, rows,
+                       e->metrics.ptr);
+  }
   IRS_HIP(hipGetLastError());
 }
 
@@ -1460,6 +1503,103 @@ void finish_accumulate(irs_evaluator *e, irs_metrics *out, int64_t *item_cnt, hi
                          hipMemcpyDeviceToHost, s));
   IRS_HIP(hipStreamSynchronize(s));
 }
+
+// ---- shared by the dense-similarity and factor-model calls (irs_eval_get_metrics_dense_similarity / _factors) ----
+
+// The mask rows that arrive with a call (rows + 1 pointers, NULL = no mask; the conventions of
+// irs_eval_get_metrics_masked), checked on the host - pointers that do not decrease, columns inside
+// [0, n_items) -, rebased to 0 and uploaded.  `ptr.ptr` stays null when nothing is masked.
+struct CallMask {
+  DeviceBuffer<int64_t> ptr;
+  DeviceBuffer<int32_t> idx;
+  void upload(const int64_t *mask_indptr, const int32_t *mask_indices, int64_t rows, int64_t n_items, hipStream_t s) {
+    const int64_t nnz = mask_indptr ? mask_indptr[rows] - mask_indptr[0] : 0;
+    if (rows <= 0 || nnz <= 0) return;
+    check_arg(mask_indices != nullptr, "mask_indices is null.");
+    std::vector<int64_t> mp(static_cast<size_t>(rows) + 1);
+    for (int64_t r = 0; r <= rows; r++) {
+      mp[r] = mask_indptr[r] - mask_indptr[0];
+      check_arg(mp[r] >= (r ? mp[r - 1] : 0), "mask_indptr must not decrease.");
+    }
+    std::atomic<int> bad(0);
+    parallel_ranges(nnz, [&](int64_t lo, int64_t hi) {
+      int32_t mn = 0, mx = 0;
+      for (int64_t q = lo; q < hi; q++) {
+        mn = std::min(mn, mask_indices[q]);
+        mx = std::max(mx, mask_indices[q]);
+      }
+      if (mn < 0 || mx >= n_items) bad.store(1);
+    });
+    check_arg(bad.load() == 0, "mask column index out of range.");
+    ptr.upload(mp, s);
+    idx.upload(mask_indices, static_cast<size_t>(nnz), s);
+  }
+};
+
+// Where the stream time of such a call went (irs_eval_last_phases): an event after every phase of every
+// block, read after the call's last synchronisation.
+enum Phase { PH_UPLOAD = 0, PH_SCORE = 1, PH_MASK = 2, PH_RANK = 3, PH_COUNT = 4 };
+struct PhaseClock {
+  std::vector<std::pair<hipEvent_t, int>> marks;  // (event, phase that ended there; -1: the start)
+  hipStream_t s;
+  explicit PhaseClock(hipStream_t stream) : s(stream) { mark(-1); }
+  ~PhaseClock() {
+    for (auto &m : marks) (void)hipEventDestroy(m.first);
+  }
+  void mark(int phase) {
+    hipEvent_t ev = nullptr;
+    IRS_HIP(hipEventCreate(&ev));
+    marks.emplace_back(ev, phase);
+    IRS_HIP(hipEventRecord(ev, s));
+  }
+  void read(double *ms) const {  // (after the stream was synchronised)
+    std::fill(ms, ms + PH_COUNT, 0.0);
+    for (size_t i = 1; i < marks.size(); i++) {
+      float t = 0.0f;
+      IRS_HIP(hipEventElapsedTime(&t, marks[i - 1].first, marks[i].first));
+      ms[marks[i].second] += t;
+    }
+  }
+};
+
+// Per cutoff the running totals of a call's blocks, on the device: every block is ranked once per cutoff, its
+// per-user terms merged in the order of the Evaluator's default host loop (HOST_LOOP_ROWS-row chunks in sequence:
+// the blocks of a call are multiples of that, so the chunk boundaries are the loop's), its item counts added; one
+// read-back after the last block.
+struct CutoffTotals {
+  DeviceBuffer<irs_metrics> m;
+  DeviceBuffer<unsigned long long> cnt;
+  void begin(int32_t n_cutoffs, int64_t ni, hipStream_t s) {
+    const size_t nc = static_cast<size_t>(std::max(n_cutoffs, 1));
+    m.alloc(nc);
+    cnt.alloc(nc * static_cast<size_t>(std::max<int64_t>(ni, 1)));
+    m.zero(s);
+    cnt.zero(s);
+  }
+  template <class T>
+  void add_block(irs_evaluator *e, const T *scores, int64_t rows, int32_t n_cutoffs, const int64_t *cutoffs,
+                 int64_t offset, bool rwc, hipStream_t s) {
+    const int64_t ni = e->n_items;
+    for (int32_t c = 0; c < n_cutoffs; c++) {
+      begin_accumulate(e, s);
+      rank_block<T>(e, scores, rows, cutoffs[c], offset, rwc, s, m.ptr + c);
+      if (ni > 0)
+        hipLaunchKernelGGL(counts_fold_kernel, dim3(static_cast<unsigned>(ceil_div(ni, 256))), dim3(256), 0, s,
+                           static_cast<const unsigned long long *>(e->item_cnt.ptr), ni, cnt.ptr + static_cast<size_t>(c) * ni);
+    }
+    IRS_HIP(hipGetLastError());
+  }
+  void finish(int32_t n_cutoffs, int64_t ni, irs_metrics *out, int64_t *item_cnt, hipStream_t s) {
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "");
+    if (n_cutoffs > 0) {
+      IRS_HIP(hipMemcpyAsync(out, m.ptr, sizeof(irs_metrics) * static_cast<size_t>(n_cutoffs), hipMemcpyDeviceToHost, s));
+      if (ni > 0)
+        IRS_HIP(hipMemcpyAsync(item_cnt, cnt.ptr, sizeof(int64_t) * static_cast<size_t>(n_cutoffs) * ni,
+                               hipMemcpyDeviceToHost, s));
+    }
+    IRS_HIP(hipStreamSynchronize(s));
+  }
+};
 
 
 bool ensure_mask_bitmap(irs_evaluator *e, int64_t rows, int64_t words, const int64_t *d_mptr,
@@ -2225,6 +2365,180 @@ irs_status irs_eval_get_metrics_similarity(irs_evaluator *e, int64_t begin, int6
                                hipMemcpyDeviceToHost, s));
     }
     IRS_HIP(hipStreamSynchronize(s));
+  });
+}
+
+irs_status irs_eval_get_metrics_dense_similarity(irs_evaluator *e, int64_t begin, int64_t end, int64_t n_model_users,
+                                                 int64_t n_profile_cols, const int64_t *x_indptr,
+                                                 const int32_t *x_indices, const double *x_data, int32_t w_is_f64,
+                                                 const void *w, const int64_t *mask_indptr,
+                                                 const int32_t *mask_indices, int32_t n_cutoffs, const int64_t *cutoffs,
+                                                 int64_t offset, int32_t recall_with_cutoff, irs_metrics *out,
+                                                 int64_t *item_cnt) {
+  return guard([&] {
+    check_arg(e && out && item_cnt && cutoffs && x_indptr, "null argument.");
+    check_arg(0 <= begin && begin <= end && end <= n_model_users, "user range out of bounds.");
+    check_arg(n_cutoffs >= 0, "negative count.");
+    const int64_t rows = end - begin, ni = e->n_items, np_ = n_profile_cols;
+    for (int32_t c = 0; c < n_cutoffs; c++) validate_call(e, rows, cutoffs[c], offset, 1);
+    check_arg(np_ >= 0 && np_ < (int64_t(1) << 31), "bad profile width.");
+    check_arg(x_indptr[0] == 0, "malformed indptr.");
+    for (int64_t r = begin; r < end; r++) check_arg(x_indptr[r + 1] >= x_indptr[r], "malformed indptr.");
+    const int64_t xq0 = x_indptr[begin], x_nnz = x_indptr[end] - xq0;
+    check_arg(x_nnz == 0 || (x_indices && x_data), "null argument.");
+    check_arg(np_ == 0 || ni == 0 || w != nullptr, "null argument.");
+    std::atomic<int> bad(0);
+    parallel_ranges(x_nnz, [&](int64_t lo, int64_t hi) {
+      int32_t mn = 0, mx = 0;
+      for (int64_t q = lo; q < hi; q++) {
+        mn = std::min(mn, x_indices[xq0 + q]);
+        mx = std::max(mx, x_indices[xq0 + q]);
+      }
+      if (hi > lo && (mn < 0 || mx >= np_)) bad.store(1);
+    });
+    check_arg(bad.load() == 0, "column index out of range.");
+    IRS_HIP(hipSetDevice(e->device));
+    hipStream_t s = nullptr;
+    PhaseClock clock(s);
+    // uploads: the profile rows as they are stored, W (once per call, never kept: a tuning loop evaluates every
+    // fitted W once), the mask rows
+    DeviceBuffer<int64_t> d_xp;
+    DeviceBuffer<int32_t> d_xi;
+    DeviceBuffer<double> d_xv;
+    DeviceBuffer<char> d_w;
+    std::vector<int64_t> xp(static_cast<size_t>(rows) + 1);
+    for (int64_t r = 0; r <= rows; r++) xp[r] = x_indptr[begin + r] - xq0;
+    d_xp.upload(xp, s);
+    d_xi.upload(x_indices + xq0, static_cast<size_t>(x_nnz), s);
+    d_xv.upload(x_data + xq0, static_cast<size_t>(x_nnz), s);
+    if (rows > 0 && x_nnz > 0)
+      d_w.upload(static_cast<const char *>(w), static_cast<size_t>(np_) * ni * (w_is_f64 ? 8 : 4), s);
+    CallMask mask;
+    mask.upload(mask_indptr, mask_indices, rows, ni, s);
+    // blocks of users whose float64 scores fit 4 GB, as in irs_eval_get_metrics_similarity
+    int64_t per = std::max<int64_t>(1, std::min<int64_t>(rows, (int64_t(1) << 32) / std::max<int64_t>(8 * ni, 1)));
+    if (per < rows && per >= HOST_LOOP_ROWS) per = per / HOST_LOOP_ROWS * HOST_LOOP_ROWS;  // (whole chunks of the host loop)
+    if (const char *v = std::getenv("IRSPACK_AMD_EVAL_SIM_BLOCK_ROWS"))  // (tests: several blocks on a small call)
+      per = std::max<int64_t>(1, std::min<int64_t>(per, std::atoll(v)));
+    const int64_t n_strips = ceil_div(std::max<int64_t>(ni, 1), DS_STRIP);
+    check_arg(per * n_strips < (int64_t(1) << 31), "score block too large for one launch.");
+    CutoffTotals totals;
+    totals.begin(n_cutoffs, ni, s);
+    std::fill(item_cnt, item_cnt + static_cast<int64_t>(std::max(n_cutoffs, 0)) * ni, int64_t(0));
+    // launch order inside every block: rows by stored profile length, longest first (counting sort, stable)
+    DeviceBuffer<int32_t> d_order;
+    if (rows > 0 && ni > 0) {
+      e->score_buf.alloc(static_cast<size_t>(per) * ni * 8);
+      std::vector<int32_t> order(static_cast<size_t>(rows));
+      constexpr int64_t CAP = 1 << 16;
+      std::vector<int32_t> start(CAP + 2);
+      for (int64_t b = 0; b < rows; b += per) {
+        const int64_t m = std::min(per, rows - b);
+        std::fill(start.begin(), start.end(), 0);
+        auto len = [&](int64_t r) { return std::min<int64_t>(CAP, xp[b + r + 1] - xp[b + r]); };
+        for (int64_t r = 0; r < m; r++) start[CAP - len(r) + 1]++;
+        for (size_t i = 1; i < start.size(); i++) start[i] += start[i - 1];
+        for (int64_t r = 0; r < m; r++) order[b + start[CAP - len(r)]++] = static_cast<int32_t>(r);
+      }
+      d_order.upload(order, s);
+    }
+    clock.mark(PH_UPLOAD);
+    for (int64_t b = 0; b < rows && ni > 0; b += per) {
+      const int64_t m = std::min(per, rows - b);
+      double *scores = reinterpret_cast<double *>(e->score_buf.ptr);
+      const dim3 grid(static_cast<unsigned>(m * n_strips));
+      if (x_nnz == 0)  // (no profile entry in the whole call: W was not uploaded, every score is 0)
+        IRS_HIP(hipMemsetAsync(scores, 0, static_cast<size_t>(m) * ni * 8, s));
+      else if (w_is_f64)
+        hipLaunchKernelGGL(dense_sim_score_kernel<double>, grid, dim3(64), 0, s, static_cast<const int64_t *>(d_xp.ptr),
+                           static_cast<const int32_t *>(d_xi.ptr), static_cast<const double *>(d_xv.ptr),
+                           reinterpret_cast<const double *>(d_w.ptr), b, m, ni, scores,
+                           static_cast<const int32_t *>(d_order.ptr) + b);
+      else
+        hipLaunchKernelGGL(dense_sim_score_kernel<float>, grid, dim3(64), 0, s, static_cast<const int64_t *>(d_xp.ptr),
+                           static_cast<const int32_t *>(d_xi.ptr), static_cast<const double *>(d_xv.ptr),
+                           reinterpret_cast<const float *>(d_w.ptr), b, m, ni, scores,
+                           static_cast<const int32_t *>(d_order.ptr) + b);
+      IRS_HIP(hipGetLastError());
+      clock.mark(PH_SCORE);
+      if (mask.ptr.ptr)
+        hipLaunchKernelGGL(mask_block_kernel<double>, dim3(static_cast<unsigned>(m)), dim3(64), 0, s, scores, m, ni,
+                           static_cast<const int64_t *>(mask.ptr.ptr) + b, static_cast<const int32_t *>(mask.idx.ptr));
+      IRS_HIP(hipGetLastError());
+      clock.mark(PH_MASK);
+      totals.add_block<double>(e, scores, m, n_cutoffs, cutoffs, offset + b, recall_with_cutoff != 0, s);
+      clock.mark(PH_RANK);
+    }
+    totals.finish(n_cutoffs, ni, out, item_cnt, s);
+    clock.read(e->phase_ms);
+  });
+}
+
+irs_status irs_eval_get_metrics_factors(irs_evaluator *e, int64_t begin, int64_t end, int64_t n_model_users, int32_t k,
+                                        const float *user_factors, const float *item_factors,
+                                        const int64_t *mask_indptr, const int32_t *mask_indices, int32_t n_cutoffs,
+                                        const int64_t *cutoffs, int64_t offset, int32_t recall_with_cutoff,
+                                        irs_metrics *out, int64_t *item_cnt) {
+  return guard([&] {
+    check_arg(e && out && item_cnt && cutoffs, "null argument.");
+    check_arg(0 <= begin && begin <= end && end <= n_model_users, "user range out of bounds.");
+    check_arg(n_cutoffs >= 0, "negative count.");
+    check_arg(k >= 1 && k <= 576, "the number of factors must lie in 1 .. 576.");
+    const int64_t rows = end - begin, ni = e->n_items;
+    for (int32_t c = 0; c < n_cutoffs; c++) validate_call(e, rows, cutoffs[c], offset, 1);
+    check_arg((rows == 0 || user_factors) && (ni == 0 || item_factors), "null argument.");
+    IRS_HIP(hipSetDevice(e->device));
+    hipStream_t s = nullptr;
+    PhaseClock clock(s);
+    // the factor tables, rows zero-padded to KP (a multiple of 32) on the way up: what the MFMA tiles read
+    const int32_t KP = (k + 31) / 32 * 32;
+    DeviceBuffer<float> d_user, d_item;
+    auto upload_padded = [&](DeviceBuffer<float> &d, const float *host, int64_t n) {
+      d.alloc(static_cast<size_t>(std::max<int64_t>(n, 1)) * KP);
+      d.zero(s);
+      if (n > 0)
+        IRS_HIP(hipMemcpy2DAsync(d.ptr, sizeof(float) * KP, host, sizeof(float) * k, sizeof(float) * k,
+                                 static_cast<size_t>(n), hipMemcpyHostToDevice, s));
+    };
+    upload_padded(d_user, rows > 0 ? user_factors + begin * static_cast<int64_t>(k) : nullptr, rows);
+    upload_padded(d_item, item_factors, ni);
+    CallMask mask;
+    mask.upload(mask_indptr, mask_indices, rows, ni, s);
+    // users scored and ranked per pass: as in irs_eval_get_metrics_ials
+    const int64_t fit = (int64_t(1) << 31) / (std::max<int64_t>(ni, 1) * 4);
+    int64_t block_cap = 16384;
+    if (const char *eb = std::getenv("IRSPACK_AMD_EVAL_BLOCK"))
+      block_cap = std::max<int64_t>(256, std::atoll(eb) / HOST_LOOP_ROWS * HOST_LOOP_ROWS);
+    const int64_t BLOCK = std::min<int64_t>(block_cap, std::max<int64_t>(1024, fit / 1024 * 1024));
+    CutoffTotals totals;
+    totals.begin(n_cutoffs, ni, s);
+    std::fill(item_cnt, item_cnt + static_cast<int64_t>(std::max(n_cutoffs, 0)) * ni, int64_t(0));
+    DeviceBuffer<float> &scores = e->fused_scores;
+    if (rows > 0 && ni > 0) scores.alloc(static_cast<size_t>(std::min(BLOCK, rows)) * ni);
+    clock.mark(PH_UPLOAD);
+    for (int64_t b = 0; b < rows && ni > 0; b += BLOCK) {
+      const int64_t m = std::min(BLOCK, rows - b);
+      if (irs_gk_scores_device_(d_user.ptr + b * KP, d_item.ptr, KP, m, ni, scores.ptr, s) != IRS_OK)
+        throw std::runtime_error(irs_last_error());
+      clock.mark(PH_SCORE);
+      if (mask.ptr.ptr)
+        hipLaunchKernelGGL(mask_rows_kernel, dim3(static_cast<unsigned>(m)), dim3(64), 0, s, scores.ptr, m, ni,
+                           static_cast<const int64_t *>(mask.ptr.ptr) + b, static_cast<const int32_t *>(mask.idx.ptr),
+                           static_cast<const int32_t *>(nullptr));
+      IRS_HIP(hipGetLastError());
+      clock.mark(PH_MASK);
+      totals.add_block<float>(e, scores.ptr, m, n_cutoffs, cutoffs, offset + b, recall_with_cutoff != 0, s);
+      clock.mark(PH_RANK);
+    }
+    totals.finish(n_cutoffs, ni, out, item_cnt, s);
+    clock.read(e->phase_ms);
+  });
+}
+
+irs_status irs_eval_last_phases(irs_evaluator *e, double *ms) {
+  return guard([&] {
+    check_arg(e && ms, "null argument.");
+    std::copy(e->phase_ms, e->phase_ms + 4, ms);
   });
 }
 

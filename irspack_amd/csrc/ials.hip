@@ -2231,6 +2231,23 @@ irs_status irs_ials_scores_device_(irs_ials_trainer *t, int64_t begin, int64_t e
   });
 }
 
+// Internal hook for evaluator.hip's factor-model path: user[0:m] @ item^T for factor tables that belong to
+// the caller (device, [rows, KP] row-major, KP a multiple of 32 with the padded columns zero), on the
+// caller's stream and current device.  Not part of the public ABI.
+irs_status irs_gk_scores_device_(const float *user, const float *item, int32_t KP, int64_t m, int64_t n_items,
+                                 float *device_out, void *stream) {
+  return guard([&] {
+    check_arg(KP > 0 && KP % 32 == 0, "factor width must be a positive multiple of 32.");
+    check_arg(m >= 0 && n_items >= 0, "negative count.");
+    if (m == 0 || n_items == 0) return;
+    check_arg(user && item && device_out, "null argument.");
+    const int64_t waves = ceil_div(m, 64) * ceil_div(n_items, 64);
+    hipLaunchKernelGGL(gk_user_scores_kernel, dim3(ceil_div(waves, 4)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), user, item, KP, int64_t(0), m, n_items, device_out);
+    IRS_HIP(hipGetLastError());
+  });
+}
+
 // Internal hook for evaluator.hip's sample pass: user[begin:end] @ item[:n_prefix]^T into a
 // device buffer [end - begin, n_prefix] on the trainer's stream; `item_rows` (device, [n_prefix,
 // KP]) replaces the leading item rows when given, `user_rows` (device, [>= end, KP]) the user

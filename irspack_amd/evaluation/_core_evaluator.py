@@ -336,6 +336,92 @@ class EvaluatorCore:
         )
         return [Metrics._from_struct(self.n_items, sts[i], cnt[i]) for i in range(nc)]
 
+    def _call_outputs(self, cutoffs: Sequence[int]):
+        nc = len(cutoffs)
+        cut = np.asarray([int(c) for c in cutoffs], dtype=np.int64)
+        sts = (MetricsStruct * max(nc, 1))()
+        cnt = np.zeros((max(nc, 1), self.n_items), dtype=np.int64)
+        return nc, cut, sts, cnt
+
+    def get_metrics_dense_similarity(self, X: sps.csr_matrix, W: np.ndarray, begin: int, end: int,
+                                     mask: Optional["MaskRows"], mask_begin: int, cutoffs: Sequence[int],
+                                     offset: int, recall_with_cutoff: bool = False) -> List[Metrics]:
+        """``get_metrics_similarity`` for DENSE item weights (DenseSLIM / EASE, EDLAE; not in the reference):
+        ``W`` is a C-contiguous float32 or float64 ``(X.shape[1], n_items)`` array, uploaded once per call and
+        not kept.  Users ``[begin, end)`` of the CSR profiles ``X`` are scored on the device per (user, column)
+        as ``acc += x * float64(w)`` over the user's stored entries IN STORAGE ORDER, product and sum rounded
+        separately: scipy's ``X[begin:end].dot(W)`` bit for bit.  ``X`` is read as it is (its rows are neither
+        sorted nor copied into another order) and nothing is written to either operand.  Mask, cutoffs,
+        ``offset`` and the result as in ``get_metrics_similarity``; the users' terms are added in the order of
+        ``Evaluator``'s block loop at its default ``mb_size`` (128-user chunks merged in sequence), so the float64
+        sums are that loop's to the last bit."""
+        if offset < 0 or any(int(c) < 0 for c in cutoffs):
+            raise TypeError("cutoff / offset must be non-negative (size_t).")
+        if not isinstance(W, np.ndarray) or W.ndim != 2 or W.dtype not in (np.dtype("float32"), np.dtype("float64")):
+            raise ValueError("W must be a 2-D float32 or float64 ndarray.")
+        if not W.flags.c_contiguous:
+            raise ValueError("W must be C-contiguous.")
+        Xc = X if sps.isspmatrix_csr(X) else sps.csr_matrix(X)
+        if W.shape != (Xc.shape[1], self.n_items):
+            raise ValueError("W must be X.shape[1] x n_items.")
+        xp = np.ascontiguousarray(Xc.indptr, dtype=np.int64)
+        xi = np.ascontiguousarray(Xc.indices, dtype=np.int32)
+        xd = np.ascontiguousarray(Xc.data, dtype=np.float64)
+        rows = end - begin
+        nc, cut, sts, cnt = self._call_outputs(cutoffs)
+        mp, mi = (None, None) if mask is None else mask.rows(mask_begin, mask_begin + rows)
+        one_i, one_d = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.float64)
+        check(
+            lib().irs_eval_get_metrics_dense_similarity(
+                self._h, begin, end, Xc.shape[0], Xc.shape[1], ptr(xp, C.c_int64),
+                ptr(xi if xi.size else one_i, C.c_int32), ptr(xd if xd.size else one_d, C.c_double),
+                1 if W.dtype == np.float64 else 0, W.ctypes.data_as(C.c_void_p),
+                None if mp is None else ptr(mp, C.c_int64), None if mi is None else ptr(mi, C.c_int32),
+                nc, ptr(cut, C.c_int64), offset, 1 if recall_with_cutoff else 0, sts, ptr(cnt, C.c_int64),
+            )
+        )
+        return [Metrics._from_struct(self.n_items, sts[i], cnt[i]) for i in range(nc)]
+
+    def get_metrics_factors(self, user_factors: np.ndarray, item_factors: np.ndarray, begin: int, end: int,
+                            mask: Optional["MaskRows"], mask_begin: int, cutoffs: Sequence[int],
+                            offset: int, recall_with_cutoff: bool = False) -> List[Metrics]:
+        """Device path for FACTOR models (truncated SVD, NMF; not in the reference): users ``[begin, end)`` of
+        ``user_factors`` ``(n_model_users, k)`` are scored against ``item_factors`` ``(n_items, k)`` as
+        ``user_factors[u] @ item_factors.T`` in float32 (the fp32 MFMA tiles of the iALS scores, ``1 <= k <=
+        576``), masked and ranked once per cutoff without the scores crossing PCIe.  Mask, cutoffs, ``offset``
+        and the result as in ``get_metrics_similarity``; the sums in the order of the default block loop, as in
+        ``get_metrics_dense_similarity``."""
+        if offset < 0 or any(int(c) < 0 for c in cutoffs):
+            raise TypeError("cutoff / offset must be non-negative (size_t).")
+        for name, F in (("user_factors", user_factors), ("item_factors", item_factors)):
+            if not isinstance(F, np.ndarray) or F.ndim != 2:
+                raise ValueError(f"{name} must be a 2-D ndarray.")
+        k = user_factors.shape[1]
+        if item_factors.shape != (self.n_items, k):
+            raise ValueError("item_factors must be n_items x user_factors.shape[1].")
+        if not 1 <= k <= 576:
+            raise ValueError("the number of factors must lie in 1 .. 576.")
+        U = np.ascontiguousarray(user_factors, dtype=np.float32)
+        V = np.ascontiguousarray(item_factors, dtype=np.float32)
+        rows = end - begin
+        nc, cut, sts, cnt = self._call_outputs(cutoffs)
+        mp, mi = (None, None) if mask is None else mask.rows(mask_begin, mask_begin + rows)
+        check(
+            lib().irs_eval_get_metrics_factors(
+                self._h, begin, end, U.shape[0], k, ptr(U, C.c_float), ptr(V, C.c_float),
+                None if mp is None else ptr(mp, C.c_int64), None if mi is None else ptr(mi, C.c_int32),
+                nc, ptr(cut, C.c_int64), offset, 1 if recall_with_cutoff else 0, sts, ptr(cnt, C.c_int64),
+            )
+        )
+        return [Metrics._from_struct(self.n_items, sts[i], cnt[i]) for i in range(nc)]
+
+    def last_call_phases(self) -> Dict[str, float]:
+        """Stream time in milliseconds of the last ``get_metrics_dense_similarity`` / ``get_metrics_factors``
+        call by phase (measurement only): uploads, scoring, masking, ranking."""
+        ms = (C.c_double * 4)()
+        check(lib().irs_eval_last_phases(self._h, ms))
+        return dict(zip(("upload_ms", "score_ms", "mask_ms", "rank_ms"), (float(v) for v in ms)))
+
     def last_call_stats(self) -> dict:
         """What the last ``get_metrics_ials`` call did on the device (measurement only):
         which path ran, how many 64 x 64 score tiles it computed of how many, and the rows it

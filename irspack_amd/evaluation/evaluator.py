@@ -20,7 +20,10 @@ Two things are done differently from the reference's Python, with the same resul
   into them).
 * When the model is an ``irspack_amd`` ``IALSRecommender`` living on the evaluator's device,
   ``fused=True`` (the default) scores, masks and ranks on the GPU without materialising the
-  dense block at all (``irs_eval_get_metrics_ials``); tests/test_gpu_evaluator.py.
+  dense block at all (``irs_eval_get_metrics_ials``); tests/test_gpu_evaluator.py.  With ``fused=True`` the
+  other recommenders of this package are scored on the device as well (``_device_path``): similarity models
+  with sparse weights, dense item weights (EASE, EDLAE) and factor models (truncated SVD, NMF);
+  tests/test_gpu_evaluator_models.py.
 """
 
 import enum
@@ -241,8 +244,8 @@ class Evaluator:
         return trainer if getattr(trainer, "_device", None) == self.core._device else None
 
     def _similarity_weights(self, model: Any) -> Optional[Any]:
-        """``(profiles, W by rows)`` when the model scores as ``profiles[u] @ W`` with sparse float64
-        operands and nothing overrides its block scores: item-similarity models (``X_train[u] @ W``,
+        """``(profiles, W by rows)`` when the model scores as ``profiles[u] @ W`` with sparse float64 or
+        float32 operands (float32 is cast to float64, exactly) and nothing overrides its block scores: item-similarity models (``X_train[u] @ W``,
         base.py:406-429) and user-similarity models (``U[u] @ X_train``, base.py:432-453).  The row form of
         a CSC operand is kept per model."""
         from ..recommenders.base import BaseSimilarityRecommender, BaseUserSimilarityRecommender
@@ -260,17 +263,81 @@ class Evaluator:
         else:
             return None
         if W is None or profiles is None or not sps.issparse(W) or not sps.issparse(profiles) or \
-                W.dtype != np.float64 or profiles.dtype != np.float64:
+                W.dtype not in _SCORE_DTYPES or profiles.dtype not in _SCORE_DTYPES:
             return None
         held = getattr(self, "_sim_rows_held", None)
         if held is None or held[0] is not W or held[1] is not profiles:
             rows = []
             for M in (profiles, W):
                 Mr = M if sps.isspmatrix_csr(M) else sps.csr_matrix(M)
+                if Mr.dtype != np.float64:
+                    # (SLIM's float32 weights: scipy's product with a float64 operand is computed in float64
+                    # anyway and the cast is exact - a copy, the model's matrix stays as it is)
+                    Mr = Mr.astype(np.float64)
                 Mr.sort_indices()
                 rows.append(Mr)
             held = self._sim_rows_held = (W, profiles, rows[0], rows[1])
         return held[2], held[3]
+
+    def _dense_similarity_weights(self, model: Any) -> Optional[Any]:
+        """``(profiles, W)`` when the model scores as ``X_train[u] @ W`` with a DENSE ``W`` (DenseSLIM / EASE,
+        EDLAE) that the device can read as it is - a C-contiguous float32 or float64 ``(n_items, n_items)``
+        array - and nothing overrides its block scores; anything else (a Fortran-ordered ``W``) is left to the
+        block loop."""
+        from ..recommenders.base import BaseSimilarityRecommender
+
+        if not self.fused or not isinstance(model, BaseSimilarityRecommender) or \
+                type(model).get_score_block is not BaseSimilarityRecommender.get_score_block:
+            return None
+        profiles, W = model.X_train_all, getattr(model, "_W", None)
+        if not isinstance(W, np.ndarray) or W.dtype not in _SCORE_DTYPES or not W.flags.c_contiguous or \
+                W.shape != (model.n_items, model.n_items):
+            return None
+        if not sps.issparse(profiles) or profiles.dtype != np.float64:
+            return None
+        return profiles, W
+
+    def _factor_operands(self, model: Any) -> Optional[Any]:
+        """``(user factors (U, k), item factors (I, k))`` when the model scores as a float32 product of two
+        factor tables - ``z @ components_`` of the truncated SVD, ``W @ H`` of NMF - through its class's own
+        ``get_score_block``; ``None`` for anything else (other dtypes, more factors than the device call takes)."""
+        from ..recommenders.nmf import NMFRecommender
+        from ..recommenders.truncsvd import TruncatedSVDRecommender
+
+        if not self.fused:
+            return None
+        if isinstance(model, TruncatedSVDRecommender):
+            if type(model).get_score_block is not TruncatedSVDRecommender.get_score_block:
+                return None
+            users = getattr(model, "z_", None)
+            items = getattr(getattr(model, "decomposer_", None), "components_", None)
+        elif isinstance(model, NMFRecommender):
+            if type(model).get_score_block is not NMFRecommender.get_score_block:
+                return None
+            users, items = getattr(model, "W", None), getattr(model, "H", None)
+        else:
+            return None
+        for F in (users, items):
+            if not isinstance(F, np.ndarray) or F.ndim != 2 or F.dtype != np.float32:
+                return None
+        k = users.shape[1]
+        if users.shape[0] != model.n_users or items.shape != (k, model.n_items) or not 1 <= k <= 576:
+            return None
+        return users, np.ascontiguousarray(items.T)
+
+    def _device_path(self, model: Any) -> str:
+        """which way ``_evaluate_model`` takes for ``model``: ``"trainer"`` (a fusable iALS trainer),
+        ``"similarity"`` (sparse weights), ``"dense_similarity"``, ``"factors"`` - all on the device, only with
+        ``fused`` - or ``"blocks"`` (the model's ``get_score_block``, ranked block by block)"""
+        if self._fusable_trainer(model) is not None:
+            return "trainer"
+        if self._similarity_weights(model) is not None:
+            return "similarity"
+        if self._dense_similarity_weights(model) is not None:
+            return "dense_similarity"
+        if self._factor_operands(model) is not None:
+            return "factors"
+        return "blocks"
 
     def _window_of_training_matrix(self, model: Any, first: int, last: int) -> Any:
         """rows [first, last) of the model's training matrix as the fused path's mask: the whole
@@ -297,17 +364,20 @@ class Evaluator:
             return [self._with_coverage(self.core.get_metrics_ials(trainer, first, last, mask, c, 0,
                                                                    self.recall_with_cutoff))
                     for c in cutoffs]
-        sim = self._similarity_weights(model)
-        if sim is not None:
-            profiles, W = sim
-            # score = X_train[u] @ W on the device (the host product bit for bit), masked and ranked there:
-            # what the block loop below does per `mb_size` users through scipy and PCIe
+        # score = X_train[u] @ W (the host product bit for bit) or the product of two factor tables on the
+        # device, masked and ranked there: what the block loop below does per `mb_size` users through scipy /
+        # numpy and PCIe
+        for operands, call in ((self._similarity_weights, self.core.get_metrics_similarity),
+                               (self._dense_similarity_weights, self.core.get_metrics_dense_similarity),
+                               (self._factor_operands, self.core.get_metrics_factors)):
+            found = operands(model)
+            if found is None:
+                continue
             if self.masked_interactions is None:
                 mask, mask_begin = self._mask_rows(model.X_train_all), first
             else:
                 mask, mask_begin = self._mask_rows(self.masked_interactions), 0
-            ranked = self.core.get_metrics_similarity(profiles, W, first, last, mask, mask_begin,
-                                                      cutoffs, 0, self.recall_with_cutoff)
+            ranked = call(found[0], found[1], first, last, mask, mask_begin, cutoffs, 0, self.recall_with_cutoff)
             return [self._with_coverage(m) for m in ranked]
         # blocks are numbered by MODEL user: the ground truth starts at `offset`; an explicit mask is
         # indexed like the ground truth, the training matrix like the model
