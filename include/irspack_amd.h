@@ -635,6 +635,57 @@ irs_status irs_nmf_fit(int64_t n_users, int64_t n_items, const int64_t *indptr, 
                        float l2_H, double tol, int64_t max_iter, int32_t update_H, int32_t device, int64_t *n_iter,
                        double *violations /* may be NULL */, irs_nmf_stats_t *stats /* may be NULL */);
 
+/* ------------------------------------------------------------------ serving
+ * Batch top-k recommendations from a model that stays on the device (the reference's path:
+ * utils/id_mapping.py:172-223, 399-453 - get_score_remove_seen on the host, then
+ * retrieve_recommend_from_score, util.hpp:426-504).  A server holds the item-side operand of one model,
+ * validated and uploaded once by one of three constructors:
+ *   similarity        W [n_profile_cols, n_items] as CSR by rows, float64 (item-kNN, P3alpha, RP3beta, SLIM;
+ *                     user-kNN with W = the training matrix).  A row that stores a column twice is
+ *                     IRS_INVALID_ARGUMENT ("duplicate column in a row of W": two lanes of the score kernel
+ *                     would add to one sum at once).  Rows with increasing columns get their per-tile ranges
+ *                     here, once; other rows are walked whole.
+ *   dense similarity  W [n_profile_cols, n_items] row-major, float32 or float64 (EASE, EDLAE).
+ *   factors           item_factors [n_items, k] row-major float32, 1 <= k <= 576, rows zero-padded to a
+ *                     multiple of 32 on upload (iALS embeddings, truncated SVD, NMF).
+ * A recommend call scores `rows` rows - profiles (CSR float64 [rows, n_profile_cols]: score = profile @ W, the
+ * host product bit for bit) or user factors (float32 [rows, k]: fp32 MFMA tiles) -, sets the excluded items of
+ * every row to -inf (excl_indptr int64[rows + 1], excl_indices; NULL = none; seen and forbidden items merged by
+ * the caller), ranks the candidates and writes, with width = min(cutoff, n_items):
+ *   out_idx int32 [rows, width] (-1 padded), out_score float [rows, width] (the winners' scores narrowed to
+ *   float32, 0 in the padding), out_len int32 [rows].
+ * Allowed lists as in irs_retrieve_recommend: ragged, n_lists in {0, 1, rows}, order and duplicates kept, ids
+ * outside [0, n_items) dropped.  Best first, stop at -inf, equal scores in candidate order.  cutoff == 0 or
+ * rows == 0 gives empty results without device work; every argument error (IRS_INVALID_ARGUMENT) comes before
+ * any device work.  The rows go through in chunks of at most 16384 (IRSPACK_AMD_SERVE_BLOCK overrides the
+ * cap, at least 256) whose scores fit 2 GiB (float) / 4 GiB (double); the score block stays on the device,
+ * the three output arrays come home once per call.  Two calls give identical bytes.
+ * Threads: a server keeps ONE set of call scratch, so it runs one recommend call at a time - calls from several
+ * threads on the same server are safe and are serialised by a mutex inside it (use one server per thread to
+ * overlap them).  irs_serve_destroy must not run while another thread still uses the server.  The row, offset
+ * and list arrays are read by absolute offset: x_indptr[0], excl_indptr[0] and list_ptr[0] must not be negative. */
+typedef struct irs_server irs_server;
+irs_status irs_serve_create_similarity(int64_t n_profile_cols, int64_t n_items, const int64_t *w_indptr,
+                                       const int32_t *w_indices, const double *w_data, int32_t device,
+                                       irs_server **out);
+irs_status irs_serve_create_dense_similarity(int64_t n_profile_cols, int64_t n_items, int32_t w_is_f64,
+                                             const void *w, int32_t device, irs_server **out);
+irs_status irs_serve_create_factors(int64_t n_items, int32_t k, const float *item_factors, int32_t device,
+                                    irs_server **out);
+irs_status irs_serve_destroy(irs_server *s);
+irs_status irs_serve_recommend_profiles(irs_server *s, int64_t rows, const int64_t *x_indptr,
+                                        const int32_t *x_indices, const double *x_data,
+                                        const int64_t *excl_indptr, const int32_t *excl_indices, int64_t n_lists,
+                                        const int64_t *list_ptr, const int64_t *list_items, int64_t cutoff,
+                                        int32_t *out_idx, float *out_score, int32_t *out_len);
+irs_status irs_serve_recommend_factors(irs_server *s, int64_t rows, const float *user_factors,
+                                       const int64_t *excl_indptr, const int32_t *excl_indices, int64_t n_lists,
+                                       const int64_t *list_ptr, const int64_t *list_items, int64_t cutoff,
+                                       int32_t *out_idx, float *out_score, int32_t *out_len);
+/* Stream time of the last recommend call by phase, in milliseconds (measurement only): ms[0] uploads,
+ * ms[1] scoring, ms[2] exclusions, ms[3] ranking, the output stage and the copies home. */
+irs_status irs_serve_last_phases(irs_server *s, double *ms);
+
 /* ------------------------------------------------------------ measurement
  * No reference counterpart: SURVEY.md 8(d) asks for ceilings MEASURED on the box next to the
  * spec peaks.  Runs a 1 GiB device copy and STREAM triad (HBM bytes moved / time), a loop of

@@ -206,6 +206,13 @@ EXPORTED_SYMBOLS = [
     "irs_eval_cache_mask",
     "irs_eval_last_stats",
     "irs_fingerprint",
+    "irs_serve_create_similarity",
+    "irs_serve_create_dense_similarity",
+    "irs_serve_create_factors",
+    "irs_serve_destroy",
+    "irs_serve_recommend_profiles",
+    "irs_serve_recommend_factors",
+    "irs_serve_last_phases",
     "irs_measure_ceilings",
 ]
 
@@ -244,6 +251,21 @@ ARGTYPES = {
         C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int64), C.c_int64, C.c_int32,
         C.c_void_p, C.POINTER(C.c_int64)],
     "irs_eval_last_phases": [C.c_void_p, C.POINTER(C.c_double)],
+    "irs_serve_create_similarity": [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_void_p)],
+    "irs_serve_create_dense_similarity": [C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
+                                          C.POINTER(C.c_void_p)],
+    "irs_serve_create_factors": [C.c_int64, C.c_int32, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_void_p)],
+    "irs_serve_destroy": [C.c_void_p],
+    "irs_serve_recommend_profiles": [
+        C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+        C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+        C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_int32)],
+    "irs_serve_recommend_factors": [
+        C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int64,
+        C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_float),
+        C.POINTER(C.c_int32)],
+    "irs_serve_last_phases": [C.c_void_p, C.POINTER(C.c_double)],
 }
 
 _lib: Optional[C.CDLL] = None

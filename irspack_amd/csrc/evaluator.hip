@@ -111,7 +111,11 @@ constexpr int RANK_MAXQ = 32;
 // the selected lists are kept in global scratch instead of LDS (a workgroup's own global stores
 // are visible to its other waves after __syncthreads: they share the CU's L1), everything else
 // is the same code.
-template <class T, int NT, int MODE, int MAXQ = RANK_MAXQ, bool BIG = false>
+// POS (the serving calls, retrieve = 1 with candidate lists): the selected entries carry the candidate's POSITION in
+// its list instead of its item, so equal scores come out in candidate order whatever the order of the list
+// (util.hpp:426-504 through a stable sort); the item is looked up when the list is written.  The evaluator's lists
+// are sorted and without duplicates, where the two orders are the same.
+template <class T, int NT, int MODE, int MAXQ = RANK_MAXQ, bool BIG = false, bool POS = false>
 __global__ __launch_bounds__(NT, MODE == 2 ? 4 : 1) void rank_rows_kernel(EvalParams p) {
   using KeyT = typename KeyStore<T>::type;
   constexpr int NWV = NT / 64;
@@ -168,6 +172,10 @@ __global__ __launch_bounds__(NT, MODE == 2 ? 4 : 1) void rank_rows_kernel(EvalPa
     list = p.rec_items + cb;
   }
   auto item_of = [&](int64_t j) -> int32_t { return list ? list[j] : static_cast<int32_t>(j); };
+  auto sel_of = [&](int64_t j) -> int32_t {  // what a selected entry carries (and ties are ordered by)
+    if constexpr (POS) return static_cast<int32_t>(j);
+    else return item_of(j);
+  };
   auto key_from_scores = [&](int64_t j) -> uint64_t {
     const T s = srow[item_of(j)];
     return is_neg_inf(s) ? KEY_SKIP : order_key(s);
@@ -310,7 +318,7 @@ __global__ __launch_bounds__(NT, MODE == 2 ? 4 : 1) void rank_rows_kernel(EvalPa
         const int pos = atomicAdd(&sh_count, 1);
         if (pos < sel_cap) {
           sel_key[pos] = k;
-          sel_idx[pos] = item_of(j);
+          sel_idx[pos] = sel_of(j);
         }
       }
       return true;
@@ -397,7 +405,7 @@ __global__ __launch_bounds__(NT, MODE == 2 ? 4 : 1) void rank_rows_kernel(EvalPa
       if (inclusive ? k >= thr : k > thr) {
         const int pos = atomicAdd(&sh_count, 1);
         sel_key[pos] = k;
-        sel_idx[pos] = item_of(j);
+        sel_idx[pos] = sel_of(j);
       } else if (k == thr) {
         tie = true;
       }
@@ -417,7 +425,7 @@ __global__ __launch_bounds__(NT, MODE == 2 ? 4 : 1) void rank_rows_kernel(EvalPa
     if (tie && rank < need) {
       const int pos = atomicAdd(&sh_count, 1);
       sel_key[pos] = k;
-      sel_idx[pos] = item_of(j);
+      sel_idx[pos] = sel_of(j);
     }
     seen += __popcll(bal);
     return true;
@@ -446,7 +454,7 @@ __global__ __launch_bounds__(NT, MODE == 2 ? 4 : 1) void rank_rows_kernel(EvalPa
       }
     }
     if (p.retrieve) {
-      if (ln < n_rec) rec_row[ln] = mi;
+      if (ln < n_rec) rec_row[ln] = POS ? item_of(mi) : mi;
       return;
     }
     bool hit = false;
@@ -520,7 +528,7 @@ __global__ __launch_bounds__(NT, MODE == 2 ? 4 : 1) void rank_rows_kernel(EvalPa
     }
   }
   if (p.retrieve) {
-    for (int i = tid; i < n_rec; i += NT) rec_row[i] = sel_idx[i];
+    for (int i = tid; i < n_rec; i += NT) rec_row[i] = POS ? item_of(sel_idx[i]) : sel_idx[i];
     return;
   }
   // --- hits, histogram, output list
@@ -1274,6 +1282,7 @@ __global__ __launch_bounds__(64) void sim_score_kernel(const int64_t *__restrict
 }  // namespace eval
 }  // namespace irs
 #include "eval_dense_kernels.hpp"
+#include "serve_kernels.hpp"
 
 using namespace irs;
 using namespace irs::eval;
@@ -1348,7 +1357,7 @@ void validate_call(irs_evaluator *e, int64_t rows, int64_t cutoff, int64_t offse
 // big_cap entries per row), at most ~1 GiB of it: the rows go through in launches of
 // `per` rows.  Rare (the reference's callers use cutoffs of 5..100), so the goal is only to be
 // correct for every cutoff the reference accepts and not slower than its partial_sort.
-template <class T> void launch_rank_big(EvalParams p, int64_t max_cand, hipStream_t s) {
+template <class T, bool POS = false> void launch_rank_big(EvalParams p, int64_t max_cand, hipStream_t s) {
   int64_t cap = 1;
   while (cap < p.cutoff) cap <<= 1;
   const int64_t per = std::max<int64_t>(1, std::min<int64_t>(p.rows, (int64_t(1) << 30) / (cap * 13)));
@@ -1368,22 +1377,22 @@ template <class T> void launch_rank_big(EvalParams p, int64_t max_cand, hipStrea
     const unsigned m = static_cast<unsigned>(std::min<int64_t>(per, p.rows - b));
     p.row_base = b;
     if (key_bytes <= 128 * 1024) {
-      auto kernel = rank_rows_kernel<T, 1024, 1, RANK_MAXQ, true>;
+      auto kernel = rank_rows_kernel<T, 1024, 1, RANK_MAXQ, true, POS>;
       IRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                   hipFuncAttributeMaxDynamicSharedMemorySize,
                                   static_cast<int>(key_bytes)));
       hipLaunchKernelGGL(kernel, dim3(m), dim3(1024), key_bytes, s, p);
     } else {
-      hipLaunchKernelGGL((rank_rows_kernel<T, 256, 0, RANK_MAXQ, true>), dim3(m), dim3(256), 0, s, p);
+      hipLaunchKernelGGL((rank_rows_kernel<T, 256, 0, RANK_MAXQ, true, POS>), dim3(m), dim3(256), 0, s, p);
     }
   }
   IRS_HIP(hipGetLastError());
   IRS_HIP(hipStreamSynchronize(s));  // the scratch is released on return
 }
 
-template <class T> void launch_rank(EvalParams p, int64_t max_cand, hipStream_t s, int32_t *todo) {
+template <class T, bool POS = false> void launch_rank(EvalParams p, int64_t max_cand, hipStream_t s, int32_t *todo) {
   if (p.cutoff > SEL_CAP) {
-    launch_rank_big<T>(p, max_cand, s);
+    launch_rank_big<T, POS>(p, max_cand, s);
     return;
   }
   // the usual case first (all items are candidates, cutoff <= 64): one wave per row; the
@@ -1405,15 +1414,15 @@ template <class T> void launch_rank(EvalParams p, int64_t max_cand, hipStream_t 
   // key cache in LDS when a row's candidates fit next to the 28 KB of static LDS
   const size_t key_bytes = static_cast<size_t>(std::max<int64_t>(max_cand, 1)) * sizeof(typename KeyStore<T>::type);
   if (std::is_same<T, float>::value && max_cand <= 1024 * RANK_MAXQ) {
-    hipLaunchKernelGGL((rank_rows_kernel<T, 1024, 2>), dim3(p.rows), dim3(1024), 0, s, p);
+    hipLaunchKernelGGL((rank_rows_kernel<T, 1024, 2, RANK_MAXQ, false, POS>), dim3(p.rows), dim3(1024), 0, s, p);
   } else if (key_bytes <= 128 * 1024) {
-    auto kernel = rank_rows_kernel<T, 1024, 1>;
+    auto kernel = rank_rows_kernel<T, 1024, 1, RANK_MAXQ, false, POS>;
     IRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                 hipFuncAttributeMaxDynamicSharedMemorySize,
                                 static_cast<int>(key_bytes)));
     hipLaunchKernelGGL(kernel, dim3(p.rows), dim3(1024), key_bytes, s, p);
   } else {
-    hipLaunchKernelGGL((rank_rows_kernel<T, 256, 0>), dim3(p.rows), dim3(256), 0, s, p);
+    hipLaunchKernelGGL((rank_rows_kernel<T, 256, 0, RANK_MAXQ, false, POS>), dim3(p.rows), dim3(256), 0, s, p);
   }
 }
 
@@ -2765,6 +2774,407 @@ irs_status irs_retrieve_recommend(int32_t is_f64, const void *scores, int64_t ro
     IRS_HIP(hipMemcpyAsync(out_idx, d_rec.ptr, static_cast<size_t>(rows) * cutoff * sizeof(int32_t),
                            hipMemcpyDeviceToHost, s));
     IRS_HIP(hipStreamSynchronize(s));
+  });
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------
+// Serving: irs_serve_* (include/irspack_amd.h).  The item-side operand lives in an irs_server; a recommend call
+// uploads its rows, then per chunk: score, mask, rank (retrieve = 1), emit (serve_kernels.hpp).
+namespace {
+
+// what the two recommend calls share
+struct ServeCall {
+  int64_t rows;
+  const int64_t *excl_indptr;
+  const int32_t *excl_indices;
+  int64_t n_lists;
+  const int64_t *list_ptr;
+  const int64_t *list_items;
+  int64_t cutoff;
+  int32_t *out_idx;
+  float *out_score;
+  int32_t *out_len;
+  // filled by serve_check
+  int32_t width = 0;
+  int64_t excl_nnz = 0, max_cand = 0;
+  std::vector<int64_t> excl_ptr_host, list_ptr_host;
+  std::vector<int32_t> list_items_host;
+};
+
+// rows per chunk: as irs_eval_get_metrics_factors sizes its blocks (a 2 GiB float block - the same rows of
+// float64 scores are the 4 GB of irs_eval_get_metrics_similarity -, at most 16384 rows)
+int64_t serve_block_rows(int64_t ni) {
+  const int64_t fit = (int64_t(1) << 31) / (std::max<int64_t>(ni, 1) * 4);
+  int64_t block_cap = 16384;
+  if (const char *eb = std::getenv("IRSPACK_AMD_SERVE_BLOCK")) block_cap = std::max<int64_t>(256, std::atoll(eb));
+  return std::min<int64_t>(block_cap, std::max<int64_t>(1, fit >= 1024 ? fit / 1024 * 1024 : fit));
+}
+
+// every argument check of what the two calls share (host only); false: nothing to compute (the outputs are set)
+bool serve_check(irs_server *sv, ServeCall &c) {
+  check_arg(c.rows >= 0, "negative row count.");
+  check_arg(c.cutoff >= 0, "cutoff must not be negative.");
+  check_arg(c.n_lists == 0 || c.n_lists == 1 || c.n_lists == c.rows,
+            "allowed_indices, if not empty, must have a size equal to X.rows()");
+  check_arg(c.n_lists == 0 || c.list_ptr != nullptr, "null argument.");
+  const int64_t ni = sv->n_items;
+  c.width = static_cast<int32_t>(std::min<int64_t>(c.cutoff, ni));
+  check_arg(c.rows == 0 || c.out_len != nullptr, "null argument.");
+  check_arg(c.rows == 0 || c.width == 0 || (c.out_idx && c.out_score), "null argument.");
+  check_arg(c.rows * static_cast<int64_t>(std::max(c.width, 1)) < (int64_t(1) << 40), "output too large.");
+  // exclusion rows: pointers that do not decrease, columns inside [0, n_items); rebased to 0
+  c.excl_nnz = c.excl_indptr && c.rows > 0 ? c.excl_indptr[c.rows] - c.excl_indptr[0] : 0;
+  if (c.excl_indptr && c.rows > 0) {
+    check_arg(c.excl_indptr[0] >= 0, "excl_indptr must not be negative.");
+    c.excl_ptr_host.resize(static_cast<size_t>(c.rows) + 1);
+    for (int64_t r = 0; r <= c.rows; r++) {
+      c.excl_ptr_host[r] = c.excl_indptr[r] - c.excl_indptr[0];
+      check_arg(c.excl_ptr_host[r] >= (r ? c.excl_ptr_host[r - 1] : 0), "excl_indptr must not decrease.");
+    }
+    check_arg(c.excl_nnz == 0 || c.excl_indices != nullptr, "excl_indices is null.");
+    std::atomic<int> bad(0);
+    const int32_t *ei = c.excl_indices;
+    parallel_ranges(c.excl_nnz, [&](int64_t lo, int64_t hi) {
+      int32_t mn = 0, mx = 0;
+      for (int64_t q = lo; q < hi; q++) {
+        mn = std::min(mn, ei[q]);
+        mx = std::max(mx, ei[q]);
+      }
+      if (hi > lo && (mn < 0 || mx >= ni)) bad.store(1);
+    });
+    check_arg(bad.load() == 0, "excluded item index out of range.");
+  }
+  // candidate lists keep their order and duplicates; out-of-range ids are dropped (util.hpp:468-472)
+  c.list_ptr_host.assign(static_cast<size_t>(c.n_lists) + 1, 0);
+  c.max_cand = c.n_lists == 0 ? ni : 0;
+  check_arg(c.n_lists == 0 || c.list_ptr[0] >= 0, "list_ptr must not be negative.");
+  for (int64_t l = 0; l < c.n_lists; l++) {
+    check_arg(c.list_ptr[l + 1] >= c.list_ptr[l], "list_ptr must not decrease.");
+    check_arg(c.list_ptr[l + 1] == c.list_ptr[l] || c.list_items != nullptr, "null argument.");
+    for (int64_t q = c.list_ptr[l]; q < c.list_ptr[l + 1]; q++)
+      if (c.list_items[q] >= 0 && c.list_items[q] < ni) c.list_items_host.push_back(static_cast<int32_t>(c.list_items[q]));
+    c.list_ptr_host[l + 1] = static_cast<int64_t>(c.list_items_host.size());
+    c.max_cand = std::max(c.max_cand, c.list_ptr_host[l + 1] - c.list_ptr_host[l]);
+  }
+  check_arg(static_cast<int64_t>(c.list_items_host.size()) < (int64_t(1) << 31), "allowed lists too long.");
+  if (c.rows == 0) return false;
+  if (c.width == 0) {
+    std::fill(c.out_len, c.out_len + c.rows, 0);
+    return false;
+  }
+  return true;
+}
+
+// The chunks of a call: `score(b, m, block)` leaves the scores of the rows b .. b + m in `block`; then the
+// exclusions, the ranking and the output stage; three copies home after the last chunk.
+template <class T, class ScoreFn>
+void serve_run(irs_server *sv, ServeCall &c, hipStream_t s, PhaseClock &clock, ScoreFn &&score) {
+  const int64_t ni = sv->n_items, rows = c.rows, width = c.width;
+  if (c.excl_nnz > 0) {
+    sv->excl_ptr.upload(c.excl_ptr_host, s);
+    sv->excl_idx.upload(c.excl_indices, static_cast<size_t>(c.excl_nnz), s);
+  }
+  if (c.n_lists > 0) {
+    sv->list_ptr.upload(c.list_ptr_host, s);
+    if (c.list_items_host.empty()) c.list_items_host.push_back(0);
+    sv->list_items.upload(c.list_items_host, s);
+  }
+  const int64_t BLOCK = std::min(serve_block_rows(ni), rows);
+  sv->scores.alloc(static_cast<size_t>(BLOCK) * ni * sizeof(T));
+  sv->rec.alloc(static_cast<size_t>(BLOCK) * width);
+  sv->todo.alloc(static_cast<size_t>(BLOCK));
+  sv->row_out.alloc(static_cast<size_t>(BLOCK));
+  sv->out_idx.alloc(static_cast<size_t>(rows) * width);
+  sv->out_score.alloc(static_cast<size_t>(rows) * width);
+  sv->out_len.alloc(static_cast<size_t>(rows));
+  clock.mark(PH_UPLOAD);
+  T *block = reinterpret_cast<T *>(sv->scores.ptr);
+  for (int64_t b = 0; b < rows; b += BLOCK) {
+    const int64_t m = std::min(BLOCK, rows - b);
+    score(b, m, block);
+    IRS_HIP(hipGetLastError());
+    clock.mark(PH_SCORE);
+    if (c.excl_nnz > 0)
+      hipLaunchKernelGGL(mask_block_kernel<T>, dim3(static_cast<unsigned>(m)), dim3(64), 0, s, block, m, ni,
+                         static_cast<const int64_t *>(sv->excl_ptr.ptr) + b, static_cast<const int32_t *>(sv->excl_idx.ptr));
+    IRS_HIP(hipGetLastError());
+    clock.mark(PH_MASK);
+    EvalParams p{};
+    p.scores = block;
+    p.rows = m;
+    p.n_items = ni;
+    p.offset = b;  // (per-row lists are numbered by the call's rows)
+    p.rec_mode = c.n_lists == 0 ? 0 : (c.n_lists == 1 ? 1 : 2);
+    p.rec_ptr = sv->list_ptr.ptr;
+    p.rec_items = sv->list_items.ptr;
+    p.cutoff = static_cast<int32_t>(width);
+    p.retrieve = 1;
+    p.out = sv->row_out.ptr;
+    p.rec_out = sv->rec.ptr;
+    if (c.n_lists > 0)  // (equal scores in candidate order, whatever the order of the list)
+      launch_rank<T, true>(p, c.max_cand, s, sv->todo.ptr);
+    else
+      launch_rank<T>(p, c.max_cand, s, sv->todo.ptr);
+    hipLaunchKernelGGL(serve_emit_kernel<T>, dim3(static_cast<unsigned>(ceil_div(m, 4))), dim3(256), 0, s,
+                       static_cast<const int32_t *>(sv->rec.ptr), static_cast<const T *>(block), m, ni,
+                       static_cast<int32_t>(width), sv->out_idx.ptr + b * width, sv->out_score.ptr + b * width,
+                       sv->out_len.ptr + b);
+    IRS_HIP(hipGetLastError());
+    clock.mark(PH_RANK);
+  }
+  IRS_HIP(hipMemcpyAsync(c.out_idx, sv->out_idx.ptr, static_cast<size_t>(rows) * width * sizeof(int32_t),
+                         hipMemcpyDeviceToHost, s));
+  IRS_HIP(hipMemcpyAsync(c.out_score, sv->out_score.ptr, static_cast<size_t>(rows) * width * sizeof(float),
+                         hipMemcpyDeviceToHost, s));
+  IRS_HIP(hipMemcpyAsync(c.out_len, sv->out_len.ptr, static_cast<size_t>(rows) * sizeof(int32_t),
+                         hipMemcpyDeviceToHost, s));
+  clock.mark(PH_RANK);
+  IRS_HIP(hipStreamSynchronize(s));
+  clock.read(sv->phase_ms);
+}
+
+}  // namespace
+
+extern "C" {
+
+irs_status irs_serve_create_similarity(int64_t n_profile_cols, int64_t n_items, const int64_t *w_indptr,
+                                       const int32_t *w_indices, const double *w_data, int32_t device,
+                                       irs_server **out) {
+  return guard([&] {
+    check_arg(out && w_indptr, "null argument.");
+    const int64_t np_ = n_profile_cols, ni = n_items;
+    check_arg(np_ >= 0 && np_ < (int64_t(1) << 31) && ni >= 0 && ni < (int64_t(1) << 31), "bad shape.");
+    check_arg(w_indptr[0] == 0, "malformed indptr.");
+    for (int64_t i = 0; i < np_; i++) check_arg(w_indptr[i + 1] >= w_indptr[i], "malformed indptr.");
+    const int64_t w_nnz = w_indptr[np_];
+    check_arg(w_nnz == 0 || (w_indices && w_data), "null argument.");
+    // columns in range; a column stored twice in a row is refused (two lanes of sim_score_kernel would add to
+    // one sum at the same time); rows with increasing columns are cut into per-tile ranges
+    std::atomic<int> bad(0), dup(0), unsorted(0);
+    parallel_ranges(np_, [&](int64_t lo, int64_t hi) {
+      std::vector<int32_t> tmp;
+      for (int64_t r = lo; r < hi; r++) {
+        bool inc = true;
+        for (int64_t q = w_indptr[r]; q < w_indptr[r + 1]; q++) {
+          if (w_indices[q] < 0 || w_indices[q] >= ni) bad.store(1);
+          if (q > w_indptr[r] && w_indices[q] <= w_indices[q - 1]) inc = false;
+        }
+        if (!inc) {
+          unsorted.store(1);
+          tmp.assign(w_indices + w_indptr[r], w_indices + w_indptr[r + 1]);
+          std::sort(tmp.begin(), tmp.end());
+          if (std::adjacent_find(tmp.begin(), tmp.end()) != tmp.end()) dup.store(1);
+        }
+      }
+    }, 16, 4096);
+    check_arg(bad.load() == 0, "column index out of range.");
+    check_arg(dup.load() == 0, "duplicate column in a row of W");
+    require_device(device);
+    auto sv = std::make_unique<irs_server>();
+    sv->kind = irs_server::SPARSE;
+    sv->device = device;
+    sv->n_profile_cols = np_;
+    sv->n_items = ni;
+    sv->w_nnz = w_nnz;
+    sv->n_tiles = static_cast<int32_t>(ceil_div(std::max<int64_t>(ni, 1), SIM_TILE));
+    sv->w_tiled = unsorted.load() == 0 && w_nnz < (int64_t(1) << 31) && np_ > 0;
+    hipStream_t s = nullptr;
+    sv->w_ptr.upload(w_indptr, static_cast<size_t>(np_) + 1, s);
+    sv->w_idx.upload(w_indices, static_cast<size_t>(w_nnz), s);
+    sv->w_val.upload(w_data, static_cast<size_t>(w_nnz), s);
+    if (sv->w_tiled) {
+      const int64_t n_tp = np_ * (sv->n_tiles + 1);
+      sv->w_tptr.alloc(static_cast<size_t>(n_tp));
+      hipLaunchKernelGGL(sim_tile_ptr_kernel, dim3(static_cast<unsigned>(ceil_div(n_tp, 256))), dim3(256), 0, s,
+                         static_cast<const int64_t *>(sv->w_ptr.ptr), static_cast<const int32_t *>(sv->w_idx.ptr), np_,
+                         sv->n_tiles, sv->w_tptr.ptr);
+      IRS_HIP(hipGetLastError());
+    }
+    IRS_HIP(hipStreamSynchronize(s));
+    *out = sv.release();
+  });
+}
+
+irs_status irs_serve_create_dense_similarity(int64_t n_profile_cols, int64_t n_items, int32_t w_is_f64, const void *w,
+                                             int32_t device, irs_server **out) {
+  return guard([&] {
+    check_arg(out != nullptr, "null argument.");
+    const int64_t np_ = n_profile_cols, ni = n_items;
+    check_arg(np_ >= 0 && np_ < (int64_t(1) << 31) && ni >= 0 && ni < (int64_t(1) << 31), "bad shape.");
+    check_arg(np_ == 0 || ni == 0 || w != nullptr, "null argument.");
+    require_device(device);
+    auto sv = std::make_unique<irs_server>();
+    sv->kind = irs_server::DENSE;
+    sv->device = device;
+    sv->n_profile_cols = np_;
+    sv->n_items = ni;
+    sv->w_is_f64 = w_is_f64 ? 1 : 0;
+    hipStream_t s = nullptr;
+    if (np_ > 0 && ni > 0)
+      sv->w_dense.upload(static_cast<const char *>(w), static_cast<size_t>(np_) * ni * (w_is_f64 ? 8 : 4), s);
+    IRS_HIP(hipStreamSynchronize(s));
+    *out = sv.release();
+  });
+}
+
+irs_status irs_serve_create_factors(int64_t n_items, int32_t k, const float *item_factors, int32_t device,
+                                    irs_server **out) {
+  return guard([&] {
+    check_arg(out != nullptr, "null argument.");
+    check_arg(k >= 1 && k <= 576, "the number of factors must lie in 1 .. 576.");
+    check_arg(n_items >= 0 && n_items < (int64_t(1) << 31), "bad shape.");
+    check_arg(n_items == 0 || item_factors != nullptr, "null argument.");
+    require_device(device);
+    auto sv = std::make_unique<irs_server>();
+    sv->kind = irs_server::FACTORS;
+    sv->device = device;
+    sv->n_items = n_items;
+    sv->k = k;
+    sv->KP = (k + 31) / 32 * 32;
+    hipStream_t s = nullptr;
+    sv->item.alloc(static_cast<size_t>(std::max<int64_t>(n_items, 1)) * sv->KP);
+    sv->item.zero(s);
+    if (n_items > 0)
+      IRS_HIP(hipMemcpy2DAsync(sv->item.ptr, sizeof(float) * sv->KP, item_factors, sizeof(float) * k, sizeof(float) * k,
+                               static_cast<size_t>(n_items), hipMemcpyHostToDevice, s));
+    IRS_HIP(hipStreamSynchronize(s));
+    *out = sv.release();
+  });
+}
+
+irs_status irs_serve_destroy(irs_server *sv) {
+  return guard([&] {
+    if (sv) {
+      (void)hipSetDevice(sv->device);
+      delete sv;
+    }
+  });
+}
+
+irs_status irs_serve_last_phases(irs_server *sv, double *ms) {
+  return guard([&] {
+    check_arg(sv && ms, "null argument.");
+    std::lock_guard<std::mutex> one_call(sv->call_mutex);
+    std::copy(sv->phase_ms, sv->phase_ms + 4, ms);
+  });
+}
+
+irs_status irs_serve_recommend_profiles(irs_server *sv, int64_t rows, const int64_t *x_indptr, const int32_t *x_indices,
+                                        const double *x_data, const int64_t *excl_indptr, const int32_t *excl_indices,
+                                        int64_t n_lists, const int64_t *list_ptr, const int64_t *list_items,
+                                        int64_t cutoff, int32_t *out_idx, float *out_score, int32_t *out_len) {
+  return guard([&] {
+    check_arg(sv != nullptr, "null argument.");
+    check_arg(sv->kind == irs_server::SPARSE || sv->kind == irs_server::DENSE,
+              "this server holds factors: call irs_serve_recommend_factors.");
+    ServeCall c{rows, excl_indptr, excl_indices, n_lists, list_ptr, list_items, cutoff, out_idx, out_score, out_len};
+    check_arg(rows <= 0 || x_indptr != nullptr, "null argument.");
+    const int64_t np_ = sv->n_profile_cols, ni = sv->n_items;
+    const int64_t xq0 = rows > 0 ? x_indptr[0] : 0;
+    check_arg(xq0 >= 0, "malformed indptr.");
+    for (int64_t r = 0; r < rows; r++) check_arg(x_indptr[r + 1] >= x_indptr[r], "malformed indptr.");
+    const int64_t x_nnz = rows > 0 ? x_indptr[rows] - xq0 : 0;
+    check_arg(x_nnz == 0 || (x_indices && x_data), "null argument.");
+    check_arg(x_nnz < (int64_t(1) << 40), "profile too large.");
+    std::atomic<int> bad(0), x_not_ones(0);
+    parallel_ranges(x_nnz, [&](int64_t lo, int64_t hi) {
+      int32_t mn = 0, mx = 0;
+      uint64_t diff = 0;
+      for (int64_t q = lo; q < hi; q++) {
+        mn = std::min(mn, x_indices[xq0 + q]);
+        mx = std::max(mx, x_indices[xq0 + q]);
+        uint64_t bits;
+        std::memcpy(&bits, x_data + xq0 + q, 8);
+        diff |= bits ^ 0x3ff0000000000000ull;
+      }
+      if (hi > lo && (mn < 0 || mx >= np_)) bad.store(1);
+      if (diff) x_not_ones.store(1);
+    });
+    check_arg(bad.load() == 0, "column index out of range.");
+    if (!serve_check(sv, c)) return;
+    std::lock_guard<std::mutex> one_call(sv->call_mutex);  // (the call scratch is the handle's)
+    const int64_t BLOCK = std::min(serve_block_rows(ni), rows);
+    const int64_t n_strips = ceil_div(std::max<int64_t>(ni, 1), DS_STRIP);
+    check_arg(BLOCK * std::max<int64_t>(n_strips, sv->n_tiles) < (int64_t(1) << 31), "score block too large for one launch.");
+    IRS_HIP(hipSetDevice(sv->device));
+    hipStream_t s = nullptr;
+    PhaseClock clock(s);
+    std::vector<int64_t> xp(static_cast<size_t>(rows) + 1);
+    for (int64_t r = 0; r <= rows; r++) xp[r] = x_indptr[r] - xq0;
+    sv->x_ptr.upload(xp, s);
+    sv->x_idx.upload(x_indices + xq0, static_cast<size_t>(x_nnz), s);
+    // (the sparse kernel reads no values when they are all ones; the dense one always does)
+    const bool with_values = sv->kind == irs_server::DENSE || x_not_ones.load() != 0;
+    if (with_values) sv->x_val.upload(x_data + xq0, static_cast<size_t>(x_nnz), s);
+    // launch order inside every chunk: rows by stored profile length, longest first (counting sort, stable)
+    {
+      std::vector<int32_t> order(static_cast<size_t>(rows));
+      constexpr int64_t CAP = 1 << 16;
+      std::vector<int32_t> start(CAP + 2);
+      for (int64_t b = 0; b < rows; b += BLOCK) {
+        const int64_t m = std::min(BLOCK, rows - b);
+        std::fill(start.begin(), start.end(), 0);
+        auto len = [&](int64_t r) { return std::min<int64_t>(CAP, xp[b + r + 1] - xp[b + r]); };
+        for (int64_t r = 0; r < m; r++) start[CAP - len(r) + 1]++;
+        for (size_t i = 1; i < start.size(); i++) start[i] += start[i - 1];
+        for (int64_t r = 0; r < m; r++) order[b + start[CAP - len(r)]++] = static_cast<int32_t>(r);
+      }
+      sv->order.upload(order, s);
+    }
+    serve_run<double>(sv, c, s, clock, [&](int64_t b, int64_t m, double *block) {
+      const int32_t *order = static_cast<const int32_t *>(sv->order.ptr) + b;
+      if (x_nnz == 0) {  // (no profile entry in the whole call: every score is 0)
+        IRS_HIP(hipMemsetAsync(block, 0, static_cast<size_t>(m) * ni * 8, s));
+      } else if (sv->kind == irs_server::SPARSE) {
+        hipLaunchKernelGGL(sv->w_tiled ? sim_score_kernel<true> : sim_score_kernel<false>,
+                           dim3(static_cast<unsigned>(m * sv->n_tiles)), dim3(64), 0, s,
+                           static_cast<const int64_t *>(sv->x_ptr.ptr), static_cast<const int32_t *>(sv->x_idx.ptr),
+                           with_values ? static_cast<const double *>(sv->x_val.ptr) : static_cast<const double *>(nullptr),
+                           static_cast<const int64_t *>(sv->w_ptr.ptr), static_cast<const int32_t *>(sv->w_idx.ptr),
+                           static_cast<const double *>(sv->w_val.ptr), std::max<int64_t>(sv->w_nnz - 1, 0), b, ni,
+                           sv->n_tiles, block, sv->w_tiled ? static_cast<const int32_t *>(sv->w_tptr.ptr) : nullptr, order);
+      } else if (sv->w_is_f64) {
+        hipLaunchKernelGGL(dense_sim_score_kernel<double>, dim3(static_cast<unsigned>(m * n_strips)), dim3(64), 0, s,
+                           static_cast<const int64_t *>(sv->x_ptr.ptr), static_cast<const int32_t *>(sv->x_idx.ptr),
+                           static_cast<const double *>(sv->x_val.ptr), reinterpret_cast<const double *>(sv->w_dense.ptr), b, m,
+                           ni, block, order);
+      } else {
+        hipLaunchKernelGGL(dense_sim_score_kernel<float>, dim3(static_cast<unsigned>(m * n_strips)), dim3(64), 0, s,
+                           static_cast<const int64_t *>(sv->x_ptr.ptr), static_cast<const int32_t *>(sv->x_idx.ptr),
+                           static_cast<const double *>(sv->x_val.ptr), reinterpret_cast<const float *>(sv->w_dense.ptr), b, m,
+                           ni, block, order);
+      }
+    });
+  });
+}
+
+irs_status irs_serve_recommend_factors(irs_server *sv, int64_t rows, const float *user_factors,
+                                       const int64_t *excl_indptr, const int32_t *excl_indices, int64_t n_lists,
+                                       const int64_t *list_ptr, const int64_t *list_items, int64_t cutoff,
+                                       int32_t *out_idx, float *out_score, int32_t *out_len) {
+  return guard([&] {
+    check_arg(sv != nullptr, "null argument.");
+    check_arg(sv->kind == irs_server::FACTORS, "this server holds similarity weights: call irs_serve_recommend_profiles.");
+    ServeCall c{rows, excl_indptr, excl_indices, n_lists, list_ptr, list_items, cutoff, out_idx, out_score, out_len};
+    check_arg(rows <= 0 || user_factors != nullptr, "null argument.");
+    if (!serve_check(sv, c)) return;
+    std::lock_guard<std::mutex> one_call(sv->call_mutex);  // (the call scratch is the handle's)
+    const int64_t ni = sv->n_items;
+    const int32_t k = sv->k, KP = sv->KP;
+    IRS_HIP(hipSetDevice(sv->device));
+    hipStream_t s = nullptr;
+    PhaseClock clock(s);
+    // the user rows, zero-padded to KP on the way up: what the MFMA tiles read
+    sv->user.alloc(static_cast<size_t>(rows) * KP);
+    if (KP != k) IRS_HIP(hipMemsetAsync(sv->user.ptr, 0, static_cast<size_t>(rows) * KP * sizeof(float), s));
+    IRS_HIP(hipMemcpy2DAsync(sv->user.ptr, sizeof(float) * KP, user_factors, sizeof(float) * k, sizeof(float) * k,
+                             static_cast<size_t>(rows), hipMemcpyHostToDevice, s));
+    serve_run<float>(sv, c, s, clock, [&](int64_t b, int64_t m, float *block) {
+      if (irs_gk_scores_device_(sv->user.ptr + b * KP, sv->item.ptr, KP, m, ni, block, s) != IRS_OK)
+        throw std::runtime_error(irs_last_error());
+    });
   });
 }
 

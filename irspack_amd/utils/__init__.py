@@ -523,3 +523,7 @@ def nmf_transform(X, H: np.ndarray, alpha: float = 0.0, l1_ratio: float = 0.0, *
         return W
     _nmf_call(Xc, W, Hc, float(alpha), float(l1_ratio), float(tol), int(max_iter), False, device, stats)
     return W
+
+
+# irspack/utils/__init__.py exports the ID mappers from here (they import retrieve_recommend_from_score above)
+from .id_mapping import IDMapper, ItemIDMapper  # noqa: E402,F401
