@@ -25,6 +25,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "eval_host_prep.hpp"
 
 namespace irs {
 namespace eval {
@@ -1026,11 +1027,6 @@ __global__ void reduce_partials_kernel(const RowPartial *partials, int nb, int64
   out->map += acc[4];
 }
 
-// Rows per block of the Evaluator's host loop (`mb_size`, evaluator.py:363-367: 128 by default).  A call that
-// scores a model's users on the device adds their terms as that loop does - per chunk of this many rows the
-// sum of reduce_rows_kernel (what a 128-row block call returns), then Metrics::merge chunk after chunk onto the
-// running totals (evaluator.cpp:76-85) - so its float64 sums are the default loop's to the last bit.
-constexpr int64_t HOST_LOOP_ROWS = 128;
 __global__ void merge_partials_kernel(const RowPartial *partials, int nb, int64_t n, irs_metrics *out) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   long long v = out->valid_user;
@@ -1151,136 +1147,9 @@ __global__ void mask_block_kernel(T *scores, int64_t rows, int64_t n_items,
   }
 }
 
-
-// ---------------------------------------------------------------------------------------------------------
-// Scores of a SIMILARITY model on the device (round 6): score[u][:] = X[u][:] @ W
-// (BaseSimilarityRecommender.get_score_block, base.py:406-429: `X_train_all[begin:end].dot(W)` through
-// scipy's row-by-row sparse product).  One wave per (user, tile of SIM_TILE columns): the tile's float64
-// sums live in the wave's own LDS slab; the wave walks the user's stored (i, x) in order and, for each,
-// the stored entries (j, w) of row i of W, adding x * w to column j when it lies in the tile - product and
-// sum rounded separately (__dmul_rn / __dadd_rn), entries of the profile in storage order.  That IS the
-// order in which scipy's csr_matmat accumulates `sums[j] += x * w` for a result row, so the block is the
-// host product bit for bit (a column gets at most one update per profile entry - W's rows hold distinct
-// columns - and LDS operations of one wave execute in order: no atomics, no barriers, no dependence on
-// arrival order).  When W's rows hold strictly increasing columns (every recommender of this package) a
-// table made per call (sim_tile_ptr_kernel) gives each (row of W, tile) its range of entries, so a tile
-// reads a row's entries INSIDE it - one strip, sixteen rows in flight; otherwise every tile re-scans the
-// whole rows (two strips, eight rows in flight).
-constexpr int SIM_TILE = 2048;  // columns per wave: 16 KB of LDS, ten waves per CU (4096: 65 ms for the ML-20M model, 2048: 59, 1024: 66)
-
-__device__ __forceinline__ int64_t readlane_i64(int64_t v, int src) {
-  const uint32_t lo = __builtin_amdgcn_readlane(static_cast<uint32_t>(v), src);
-  const uint32_t hi = __builtin_amdgcn_readlane(static_cast<uint32_t>(static_cast<uint64_t>(v) >> 32), src);
-  return static_cast<int64_t>((static_cast<uint64_t>(hi) << 32) | lo);
-}
-__device__ __forceinline__ double readlane_f64(double v, int src) {
-  return __longlong_as_double(readlane_i64(__double_as_longlong(v), src));
-}
-
-// tptr[i * (n_tiles + 1) + t] = first entry of row i of W (columns increasing) whose column is >= t * SIM_TILE
-__global__ __launch_bounds__(256) void sim_tile_ptr_kernel(const int64_t *__restrict__ w_ptr,
-                                                           const int32_t *__restrict__ w_idx, int64_t n_rows,
-                                                           int32_t n_tiles, int32_t *__restrict__ tptr) {
-  const int64_t id = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (id >= n_rows * (n_tiles + 1)) return;
-  const int64_t i = id / (n_tiles + 1);
-  const int32_t t = static_cast<int32_t>(id % (n_tiles + 1));
-  int64_t lo = w_ptr[i], hi = w_ptr[i + 1];
-  const int64_t bound = static_cast<int64_t>(t) * SIM_TILE;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (w_idx[mid] < bound) lo = mid + 1;
-    else hi = mid;
-  }
-  tptr[id] = static_cast<int32_t>(lo);
-}
-
-template <bool TILED>  // TILED: w_tptr given - a row's entries inside the tile are one strip (a second one is not fetched)
-__global__ __launch_bounds__(64) void sim_score_kernel(const int64_t *__restrict__ x_ptr, const int32_t *__restrict__ x_idx,
-                                                       const double *__restrict__ x_val,  // null: all ones
-                                                       const int64_t *__restrict__ w_ptr, const int32_t *__restrict__ w_idx,
-                                                       const double *__restrict__ w_val, int64_t w_last, int64_t row0,
-                                                       int64_t n_items, int32_t n_tiles, double *__restrict__ out,
-                                                       const int32_t *__restrict__ w_tptr,
-                                                       const int32_t *__restrict__ order) {
-  __shared__ double acc[SIM_TILE];
-  const int lane = threadIdx.x;
-  const int64_t unit = blockIdx.x;
-  // row of the block: the rows are LAUNCHED longest profile first (`order`; a wave lasts as long as its
-  // user's profile, and a 9,000-item profile at the end of a block was a tail of its own)
-  const int64_t r = order[unit / n_tiles];
-  const int32_t tile = static_cast<int32_t>(unit % n_tiles);
-  const int32_t c0 = tile * SIM_TILE, width = static_cast<int32_t>(min<int64_t>(SIM_TILE, n_items - c0));
-  for (int k = lane; k < width; k += 64) acc[k] = 0.0;
-  const int64_t qb = x_ptr[row0 + r], qe = x_ptr[row0 + r + 1];
-  auto add = [&](int32_t jg, double x, double w) {  // (in program order per wave: LDS operations do not overtake)
-    const int32_t j = jg - c0;
-    if (static_cast<uint32_t>(j) < static_cast<uint32_t>(width)) acc[j] = __dadd_rn(acc[j], __dmul_rn(x, w));
-  };
-  // The walk is a chain of dependent loads (profile entry -> row bounds of W -> the row's columns and values):
-  // 64 profile entries are fetched at once (one per lane, with their row bounds), and the first 128 entries of
-  // the rows of D consecutive profile entries are in flight while an earlier row is added - one exposed round
-  // trip per 64 profile entries instead of three per entry (195 -> ~40 ms for the ML-20M model).
-  constexpr int D = TILED ? 16 : 8;  // rows in flight (TILED: one strip per row, twice the rows)
-  for (int64_t q0 = qb; q0 < qe; q0 += 64) {
-    const int64_t q = min(q0 + lane, qe - 1);
-    const int32_t i_l = x_idx[q];
-    const double x_l = x_val ? x_val[q] : 1.0;
-    // (rows of W with increasing columns: only the row's entries INSIDE this tile, from the table
-    // sim_tile_ptr_kernel made - a seventh of a row on the ML-20M shape, one strip instead of two)
-    int64_t eb_l, ee_l;
-    if constexpr (TILED) {
-      const int32_t *tp = w_tptr + static_cast<int64_t>(i_l) * (n_tiles + 1) + tile;
-      eb_l = tp[0];
-      ee_l = tp[1];
-    } else {
-      eb_l = w_ptr[i_l];
-      ee_l = w_ptr[i_l + 1];
-    }
-    const int n = static_cast<int>(min<int64_t>(64, qe - q0));
-    int32_t ja[D], jb[D];
-    double wa[D], wb[D];
-    auto fetch = [&](int slot, int k) {  // the first two strips of row k (clamped loads, masked when used)
-      const int64_t eb = readlane_i64(eb_l, k), ee = readlane_i64(ee_l, k);
-      // (unconditional: a load under a branch would drain the queue; w_last = the last valid entry, >= 0)
-      const int64_t e0 = min(eb + lane, w_last), e1 = min(eb + 64 + lane, w_last);
-      ja[slot] = w_idx[e0];
-      wa[slot] = w_val[e0];
-      if constexpr (!TILED) {
-        jb[slot] = w_idx[e1];
-        wb[slot] = w_val[e1];
-      }
-      (void)ee;
-      (void)e1;
-    };
-#pragma unroll
-    for (int d = 0; d < D; d++) fetch(d, min(d, n - 1));
-    for (int k0 = 0; k0 < n; k0 += D) {
-#pragma unroll
-      for (int d = 0; d < D; d++) {
-        const int k = k0 + d;
-        if (k < n) {  // (wave-uniform)
-          const int64_t eb = readlane_i64(eb_l, k), ee = readlane_i64(ee_l, k);
-          const double x = readlane_f64(x_l, k);
-          const int32_t j0 = ja[d], j1 = TILED ? 0 : jb[d];
-          const double w0 = wa[d], w1 = TILED ? 0.0 : wb[d];
-          if (k + D < n) fetch(d, k + D);  // (the slot's registers were copied: its next row starts now)
-          if (eb + lane < ee) add(j0, x, w0);
-          if constexpr (!TILED) {
-            if (eb + 64 + lane < ee) add(j1, x, w1);
-          }
-          // (rows above 128 entries; TILED: more than 64 of a row's entries inside one tile)
-          for (int64_t e = eb + (TILED ? 64 : 128) + lane; e < ee; e += 64) add(w_idx[e], x, w_val[e]);
-        }
-      }
-    }
-  }
-  double *dst = out + r * n_items + c0;
-  for (int k = lane; k < width; k += 64) dst[k] = acc[k];
-}
-
 }  // namespace eval
 }  // namespace irs
+#include "eval_sim_kernels.hpp"
 #include "eval_dense_kernels.hpp"
 #include "serve_kernels.hpp"
 
@@ -1469,18 +1338,7 @@ void rank_block(irs_evaluator *e, const void *d_scores, int64_t rows, int64_t cu
   IRS_HIP(hipGetLastError());
 }
 
-// Metrics::merge, evaluator.cpp:76-85: plain sums (the item histogram is merged by the caller)
-static void merge_metrics(irs_metrics &into, const irs_metrics &part) {
-  into.valid_user += part.valid_user;
-  into.total_user += part.total_user;
-  into.hit += part.hit;
-  into.recall += part.recall;
-  into.ndcg += part.ndcg;
-  into.precision += part.precision;
-  into.map += part.map;
-}
-
-// merge_metrics on the device (one thread: the same sums in the same order) and the item histogram beside it:
+// Metrics::merge (evaluator.cpp:76-85: plain sums) on the device, one thread, and the item histogram beside it:
 // a call that walks its users in blocks folds each block's result here instead of reading it back
 __global__ void metrics_fold_kernel(const irs_metrics *__restrict__ part, irs_metrics *__restrict__ into) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -1515,33 +1373,37 @@ void finish_accumulate(irs_evaluator *e, irs_metrics *out, int64_t *item_cnt, hi
 
 // ---- shared by the dense-similarity and factor-model calls (irs_eval_get_metrics_dense_similarity / _factors) ----
 
-// The mask rows that arrive with a call (rows + 1 pointers, NULL = no mask; the conventions of
-// irs_eval_get_metrics_masked), checked on the host - pointers that do not decrease, columns inside
-// [0, n_items) -, rebased to 0 and uploaded.  `ptr.ptr` stays null when nothing is masked.
+// Mask or exclusion rows checked on the host go up (nothing when nothing is stored): masked, model and serve calls
+void upload_mask_rows(const MaskRows &rows, const int32_t *indices, DeviceBuffer<int64_t> &ptr, DeviceBuffer<int32_t> &idx,
+                      hipStream_t s) {
+  if (rows.nnz <= 0) return;
+  ptr.upload(rows.ptr, s);
+  idx.upload(indices, static_cast<size_t>(rows.nnz), s);
+}
+
+// The mask rows that arrive with an evaluator call.  `ptr.ptr` stays null when nothing is masked.
 struct CallMask {
   DeviceBuffer<int64_t> ptr;
   DeviceBuffer<int32_t> idx;
-  void upload(const int64_t *mask_indptr, const int32_t *mask_indices, int64_t rows, int64_t n_items, hipStream_t s) {
-    const int64_t nnz = mask_indptr ? mask_indptr[rows] - mask_indptr[0] : 0;
-    if (rows <= 0 || nnz <= 0) return;
-    check_arg(mask_indices != nullptr, "mask_indices is null.");
-    std::vector<int64_t> mp(static_cast<size_t>(rows) + 1);
-    for (int64_t r = 0; r <= rows; r++) {
-      mp[r] = mask_indptr[r] - mask_indptr[0];
-      check_arg(mp[r] >= (r ? mp[r - 1] : 0), "mask_indptr must not decrease.");
+  MaskRows host;
+  void upload(const int64_t *mask_indptr, const int32_t *mask_indices, int64_t rows, int64_t n_items, bool check_columns,
+              hipStream_t s) {
+    host.take(mask_indptr, mask_indices, rows, n_items, check_columns);
+    upload_mask_rows(host, mask_indices, ptr, idx, s);
+  }
+  // The similarity call: its usual caller masks with the rows it scores from (`X_train[u] @ W`, seen items removed)
+  // and hands the same arrays over twice: the mask then aliases the profile rows `x` already on the device (80 MB
+  // less over PCIe on the ML-20M shape).
+  void upload_or_alias(const int64_t *mask_indptr, const int32_t *mask_indices, int64_t rows, int64_t n_items,
+                       const ProfileRows &x, const int32_t *x_indices, const DeviceBuffer<int64_t> &d_xp,
+                       const DeviceBuffer<int32_t> &d_xi, hipStream_t s) {
+    host.take(mask_indptr, mask_indices, rows, n_items, false);
+    if (host.nnz > 0 && mask_indices == x_indices + x.first && host.nnz == x.nnz && host.ptr == x.ptr) {
+      ptr.borrow(d_xp);
+      idx.borrow(d_xi);
+    } else {
+      upload_mask_rows(host, mask_indices, ptr, idx, s);
     }
-    std::atomic<int> bad(0);
-    parallel_ranges(nnz, [&](int64_t lo, int64_t hi) {
-      int32_t mn = 0, mx = 0;
-      for (int64_t q = lo; q < hi; q++) {
-        mn = std::min(mn, mask_indices[q]);
-        mx = std::max(mx, mask_indices[q]);
-      }
-      if (mn < 0 || mx >= n_items) bad.store(1);
-    });
-    check_arg(bad.load() == 0, "mask column index out of range.");
-    ptr.upload(mp, s);
-    idx.upload(mask_indices, static_cast<size_t>(nnz), s);
   }
 };
 
@@ -1571,14 +1433,18 @@ struct PhaseClock {
   }
 };
 
-// Per cutoff the running totals of a call's blocks, on the device: every block is ranked once per cutoff, its
-// per-user terms merged in the order of the Evaluator's default host loop (HOST_LOOP_ROWS-row chunks in sequence:
-// the blocks of a call are multiples of that, so the chunk boundaries are the loop's), its item counts added; one
-// read-back after the last block.
+// Per cutoff the running totals of a call's blocks, on the device: every block is ranked once per cutoff and its
+// item counts added; one read-back after the last block.  The per-user terms reach the totals in one of two orders,
+// each call keeping its own (the float64 sums differ in the last bits):
+//   CHUNKS  dense-similarity and factor calls: the Evaluator's default host loop (HOST_LOOP_ROWS-row chunks in
+//           sequence; the blocks of such a call are multiples of that, so the chunk boundaries are the loop's)
+//   BLOCKS  similarity call: the block as one block call sums it, then Metrics::merge (evaluator.cpp:76-85) per block
 struct CutoffTotals {
+  enum Order { CHUNKS, BLOCKS } order;
   DeviceBuffer<irs_metrics> m;
   DeviceBuffer<unsigned long long> cnt;
-  void begin(int32_t n_cutoffs, int64_t ni, hipStream_t s) {
+  CutoffTotals(Order order_, int32_t n_cutoffs, int64_t ni, int64_t *item_cnt, hipStream_t s) : order(order_) {
+    std::fill(item_cnt, item_cnt + static_cast<int64_t>(std::max(n_cutoffs, 0)) * ni, int64_t(0));
     const size_t nc = static_cast<size_t>(std::max(n_cutoffs, 1));
     m.alloc(nc);
     cnt.alloc(nc * static_cast<size_t>(std::max<int64_t>(ni, 1)));
@@ -1591,15 +1457,23 @@ struct CutoffTotals {
     const int64_t ni = e->n_items;
     for (int32_t c = 0; c < n_cutoffs; c++) {
       begin_accumulate(e, s);
-      rank_block<T>(e, scores, rows, cutoffs[c], offset, rwc, s, m.ptr + c);
+      if (order == CHUNKS) {
+        rank_block<T>(e, scores, rows, cutoffs[c], offset, rwc, s, m.ptr + c);
+      } else {
+        rank_block<T>(e, scores, rows, cutoffs[c], offset, rwc, s);
+        hipLaunchKernelGGL(metrics_fold_kernel, dim3(1), dim3(64), 0, s, static_cast<const irs_metrics *>(e->metrics.ptr),
+                           m.ptr + c);
+      }
       if (ni > 0)
         hipLaunchKernelGGL(counts_fold_kernel, dim3(static_cast<unsigned>(ceil_div(ni, 256))), dim3(256), 0, s,
                            static_cast<const unsigned long long *>(e->item_cnt.ptr), ni, cnt.ptr + static_cast<size_t>(c) * ni);
     }
     IRS_HIP(hipGetLastError());
   }
-  void finish(int32_t n_cutoffs, int64_t ni, irs_metrics *out, int64_t *item_cnt, hipStream_t s) {
+  void finish(irs_evaluator *e, int32_t n_cutoffs, irs_metrics *out, int64_t *item_cnt, hipStream_t s) {
     static_assert(sizeof(unsigned long long) == sizeof(int64_t), "");
+    const int64_t ni = e->n_items;
+    if (e->span_open) IRS_HIP(hipEventRecord(e->ev_last, s));
     if (n_cutoffs > 0) {
       IRS_HIP(hipMemcpyAsync(out, m.ptr, sizeof(irs_metrics) * static_cast<size_t>(n_cutoffs), hipMemcpyDeviceToHost, s));
       if (ni > 0)
@@ -1610,6 +1484,34 @@ struct CutoffTotals {
   }
 };
 
+// a factor table [n, k] goes up, rows zero-padded to KP (what the MFMA tiles read); no memset when KP == k
+void upload_padded(DeviceBuffer<float> &d, const float *host, int64_t n, int32_t k, int32_t KP, hipStream_t s) {
+  const size_t count = static_cast<size_t>(std::max<int64_t>(n, 1)) * KP;
+  d.alloc(count);
+  if (KP != k || n <= 0) IRS_HIP(hipMemsetAsync(d.ptr, 0, count * sizeof(float), s));
+  if (n > 0)
+    IRS_HIP(hipMemcpy2DAsync(d.ptr, sizeof(float) * KP, host, sizeof(float) * k, sizeof(float) * k, static_cast<size_t>(n),
+                             hipMemcpyHostToDevice, s));
+}
+
+// EvalParams of a ranking without ground truth (retrieve = 1): the `cutoff` best candidates of each row into rec_out
+EvalParams retrieve_params(const void *scores, int64_t rows, int64_t n_items, int64_t offset, int64_t n_lists,
+                           const int64_t *list_ptr, const int32_t *list_items, int64_t cutoff, RowOut *row_out,
+                           int32_t *rec_out) {
+  EvalParams p{};
+  p.scores = scores;
+  p.rows = rows;
+  p.n_items = n_items;
+  p.offset = offset;  // (per-row lists are numbered from the call's first row)
+  p.rec_mode = rec_mode_of(n_lists);
+  p.rec_ptr = list_ptr;
+  p.rec_items = list_items;
+  p.cutoff = static_cast<int32_t>(cutoff);
+  p.retrieve = 1;
+  p.out = row_out;
+  p.rec_out = rec_out;
+  return p;
+}
 
 bool ensure_mask_bitmap(irs_evaluator *e, int64_t rows, int64_t words, const int64_t *d_mptr,
                         const int32_t *d_midx, hipStream_t s, bool cacheable = true);
@@ -2084,7 +1986,7 @@ irs_status irs_eval_create(int64_t n_users, int64_t n_items, const int64_t *indp
     e->device = device;
     e->n_users = n_users;
     e->n_items = n_items;
-    e->rec_mode = n_lists == 0 ? 0 : (n_lists == 1 ? 1 : 2);
+    e->rec_mode = rec_mode_of(n_lists);
     hipStream_t s = nullptr;
     e->gt_ptr.upload(gptr, s);
     e->gt_idx.upload(gidx, s);
@@ -2166,30 +2068,21 @@ irs_status irs_eval_get_metrics_masked(irs_evaluator *e, int32_t is_f64, const v
     for (int32_t c = 0; c < n_cutoffs; c++) validate_call(e, rows, cutoffs[c], offset, n_threads);
     IRS_HIP(hipSetDevice(e->device));
     hipStream_t s = nullptr;
-    DeviceBuffer<int64_t> mptr;
-    DeviceBuffer<int32_t> midx;
+    CallMask mask;
     if (rows > 0) {
       const size_t bytes = static_cast<size_t>(rows) * e->n_items * (is_f64 ? 8 : 4);
       e->score_buf.alloc(bytes);
       IRS_HIP(hipMemcpyAsync(e->score_buf.ptr, scores, bytes, hipMemcpyHostToDevice, s));
-      const int64_t mnnz = mask_indptr ? mask_indptr[rows] - mask_indptr[0] : 0;
-      if (mnnz > 0) {
-        check_arg(mask_indices != nullptr, "mask_indices is null.");
-        std::vector<int64_t> mp(rows + 1);
-        for (int64_t r = 0; r <= rows; r++) {
-          mp[r] = mask_indptr[r] - mask_indptr[0];
-          check_arg(mp[r] >= (r ? mp[r - 1] : 0), "mask_indptr must not decrease.");
-        }
-        mptr.upload(mp, s);
-        midx.upload(mask_indices, static_cast<size_t>(mnnz), s);
+      mask.upload(mask_indptr, mask_indices, rows, e->n_items, false, s);  // (stray columns: the kernel skips them)
+      if (mask.ptr.ptr) {
         if (is_f64)
           hipLaunchKernelGGL(mask_block_kernel<double>, dim3(static_cast<unsigned>(rows)), dim3(64), 0, s,
-                             reinterpret_cast<double *>(e->score_buf.ptr), rows, e->n_items, mptr.ptr,
-                             midx.ptr);
+                             reinterpret_cast<double *>(e->score_buf.ptr), rows, e->n_items, mask.ptr.ptr,
+                             mask.idx.ptr);
         else
           hipLaunchKernelGGL(mask_block_kernel<float>, dim3(static_cast<unsigned>(rows)), dim3(64), 0, s,
-                             reinterpret_cast<float *>(e->score_buf.ptr), rows, e->n_items, mptr.ptr,
-                             midx.ptr);
+                             reinterpret_cast<float *>(e->score_buf.ptr), rows, e->n_items, mask.ptr.ptr,
+                             mask.idx.ptr);
         IRS_HIP(hipGetLastError());
       }
     }
@@ -2205,6 +2098,53 @@ irs_status irs_eval_get_metrics_masked(irs_evaluator *e, int32_t is_f64, const v
     }
   });
 }
+
+}  // extern "C"
+namespace {
+// ---- the score launches the similarity calls and the serve calls share (they stand between the entry points so
+// that the score kernels' instances keep the place in the code object that their first use, below, gives them) ----
+
+// profile rows on the device: rebased pointers, columns, values (null: all 1.0; the dense kernel always reads them)
+struct ProfileView { const int64_t *ptr; const int32_t *idx; const double *val; };
+// a sparse W by rows on the device; `tptr` (null: the rows are not in column order): per (row, tile of SIM_TILE
+// columns) the first entry inside the tile, from build_tile_table
+struct SparseWeightsView {
+  const int64_t *ptr; const int32_t *idx; const double *val;
+  int64_t nnz; int32_t n_tiles; const int32_t *tptr;
+};
+
+inline int32_t sim_tiles(int64_t ni) { return static_cast<int32_t>(ceil_div(std::max<int64_t>(ni, 1), SIM_TILE)); }
+
+void build_tile_table(DeviceBuffer<int32_t> &tptr, const DeviceBuffer<int64_t> &w_ptr, const DeviceBuffer<int32_t> &w_idx,
+                      int64_t n_rows, int32_t n_tiles, hipStream_t s) {
+  const int64_t n_tp = n_rows * (n_tiles + 1);
+  tptr.alloc(static_cast<size_t>(n_tp));
+  hipLaunchKernelGGL(sim_tile_ptr_kernel, dim3(static_cast<unsigned>(ceil_div(n_tp, 256))), dim3(256), 0, s,
+                     static_cast<const int64_t *>(w_ptr.ptr), static_cast<const int32_t *>(w_idx.ptr), n_rows, n_tiles,
+                     tptr.ptr);
+  IRS_HIP(hipGetLastError());
+}
+
+// scores of the rows row0 .. row0 + m of `x` (launched in `order`, relative to row0) into out [m, ni]
+void launch_sim_scores(const ProfileView &x, const SparseWeightsView &w, int64_t row0, int64_t m, int64_t ni, double *out,
+                       const int32_t *order, hipStream_t s) {
+  hipLaunchKernelGGL(w.tptr ? sim_score_kernel<true> : sim_score_kernel<false>, dim3(static_cast<unsigned>(m * w.n_tiles)),
+                     dim3(64), 0, s, x.ptr, x.idx, x.val, w.ptr, w.idx, w.val, std::max<int64_t>(w.nnz - 1, 0), row0, ni,
+                     w.n_tiles, out, w.tptr, order);
+}
+void launch_dense_scores(const ProfileView &x, const void *w, bool w_is_f64, int64_t row0, int64_t m, int64_t ni,
+                         double *out, const int32_t *order, hipStream_t s) {
+  const dim3 grid(static_cast<unsigned>(m * ceil_div(std::max<int64_t>(ni, 1), DS_STRIP)));
+  if (w_is_f64)
+    hipLaunchKernelGGL(dense_sim_score_kernel<double>, grid, dim3(64), 0, s, x.ptr, x.idx, x.val,
+                       static_cast<const double *>(w), row0, m, ni, out, order);
+  else
+    hipLaunchKernelGGL(dense_sim_score_kernel<float>, grid, dim3(64), 0, s, x.ptr, x.idx, x.val,
+                       static_cast<const float *>(w), row0, m, ni, out, order);
+}
+
+}  // namespace
+extern "C" {
 
 irs_status irs_eval_get_metrics_similarity(irs_evaluator *e, int64_t begin, int64_t end, int64_t n_model_users,
                                            int64_t n_profile_cols,
@@ -2224,156 +2164,61 @@ irs_status irs_eval_get_metrics_similarity(irs_evaluator *e, int64_t begin, int6
     // user-kNN (base.py:432-453: U[u] @ X): X = the user-user weights, W = the training matrix
     const int64_t np_ = n_profile_cols;
     check_arg(np_ >= 0 && np_ < (int64_t(1) << 31), "bad profile width.");
-    check_arg(x_indptr[0] == 0 && w_indptr[0] == 0, "malformed indptr.");
-    for (int64_t r = begin; r < end; r++) check_arg(x_indptr[r + 1] >= x_indptr[r], "malformed indptr.");
+    ProfileRows x;
+    x.take_pointers(x_indptr, begin, end, false);
+    check_arg(w_indptr[0] == 0, "malformed indptr.");
     for (int64_t i = 0; i < np_; i++) check_arg(w_indptr[i + 1] >= w_indptr[i], "malformed indptr.");
-    const int64_t xq0 = x_indptr[begin], xq1 = x_indptr[end], x_nnz = xq1 - xq0, w_nnz = w_indptr[np_];
-    check_arg((x_nnz == 0 || (x_indices && x_data)) && (w_nnz == 0 || (w_indices && w_data)), "null argument.");
-    std::atomic<int> bad(0), x_not_ones(0);
-    parallel_ranges(x_nnz, [&](int64_t lo, int64_t hi) {
-      int32_t mn = 0, mx = 0;
-      uint64_t diff = 0;
-      const uint64_t *vb = reinterpret_cast<const uint64_t *>(x_data + xq0);
-      for (int64_t q = lo; q < hi; q++) {
-        mn = std::min(mn, x_indices[xq0 + q]);
-        mx = std::max(mx, x_indices[xq0 + q]);
-        diff |= vb[q] ^ 0x3ff0000000000000ull;
-      }
-      if (hi > lo && (mn < 0 || mx >= np_)) bad.store(1);
-      if (diff) x_not_ones.store(1);
-    });
-    parallel_ranges(w_nnz, [&](int64_t lo, int64_t hi) {
-      int32_t mn = 0, mx = 0;
-      for (int64_t q = lo; q < hi; q++) {
-        mn = std::min(mn, w_indices[q]);
-        mx = std::max(mx, w_indices[q]);
-      }
-      if (hi > lo && (mn < 0 || mx >= ni)) bad.store(1);
-    });
-    check_arg(bad.load() == 0, "column index out of range.");
+    const int64_t w_nnz = w_indptr[np_];
+    check_arg((x.nnz == 0 || (x_indices && x_data)) && (w_nnz == 0 || (w_indices && w_data)), "null argument.");
+    x.scan_entries(x_indices, x_data, np_, true);
     // rows of W with strictly increasing columns (what every recommender of this package stores) are cut
-    // into per-tile ranges on the device; any other W takes the whole-row walk
-    std::atomic<int> w_unsorted{0};
-    parallel_ranges(np_, [&](int64_t lo, int64_t hi) {
-      int any = 0;
-      for (int64_t r = lo; r < hi; r++)
-        for (int64_t q = w_indptr[r] + 1; q < w_indptr[r + 1]; q++) any |= w_indices[q] <= w_indices[q - 1];
-      if (any) w_unsorted.store(1);
-    });
-    const bool w_tiled = w_unsorted.load() == 0 && w_nnz < (int64_t(1) << 31);
+    // into per-tile ranges on the device; any other W takes the whole-row walk.  (A column stored twice in a
+    // row is not looked for here.)
+    const WeightRowsScan w_rows = scan_weight_rows(w_indptr, w_indices, np_, ni, false);
+    check_arg(!w_rows.out_of_range, "column index out of range.");
+    const bool w_tiled = !w_rows.unsorted && w_nnz < (int64_t(1) << 31);
     IRS_HIP(hipSetDevice(e->device));
     hipStream_t s = nullptr;
     // uploads: the profile rows (values only when they are not all ones), W by rows, the mask rows
-    DeviceBuffer<int64_t> d_xp, d_wp, d_mp;
-    DeviceBuffer<int32_t> d_xi, d_wi, d_mi;
+    DeviceBuffer<int64_t> d_xp, d_wp;
+    DeviceBuffer<int32_t> d_xi, d_wi;
     DeviceBuffer<double> d_xv, d_wv;
-    std::vector<int64_t> xp(static_cast<size_t>(rows) + 1);
-    for (int64_t r = 0; r <= rows; r++) xp[r] = x_indptr[begin + r] - xq0;
-    d_xp.upload(xp, s);
-    d_xi.upload(x_indices + xq0, static_cast<size_t>(x_nnz), s);
-    if (x_not_ones.load()) d_xv.upload(x_data + xq0, static_cast<size_t>(x_nnz), s);
+    d_xp.upload(x.ptr, s);
+    d_xi.upload(x_indices + x.first, static_cast<size_t>(x.nnz), s);
+    if (!x.all_ones) d_xv.upload(x_data + x.first, static_cast<size_t>(x.nnz), s);
     d_wp.upload(w_indptr, static_cast<size_t>(np_) + 1, s);
     d_wi.upload(w_indices, static_cast<size_t>(w_nnz), s);
     d_wv.upload(w_data, static_cast<size_t>(w_nnz), s);
-    const int64_t m_nnz = mask_indptr ? mask_indptr[rows] - mask_indptr[0] : 0;
-    std::vector<int64_t> mp;
-    // (the usual caller masks with the rows it scores from - `X_train[u] @ W`, seen items removed: the same
-    // arrays, handed over twice; they are uploaded once - 80 MB less over PCIe on the ML-20M shape)
-    bool mask_is_x = false;
-    const int64_t *mask_ptr_dev = nullptr;
-    const int32_t *mask_idx_dev = nullptr;
-    if (m_nnz > 0) {
-      check_arg(mask_indices != nullptr, "mask_indices is null.");
-      mp.resize(static_cast<size_t>(rows) + 1);
-      for (int64_t r = 0; r <= rows; r++) {
-        mp[r] = mask_indptr[r] - mask_indptr[0];
-        check_arg(mp[r] >= (r ? mp[r - 1] : 0), "mask_indptr must not decrease.");
-      }
-      mask_is_x = mask_indices == x_indices + xq0 && m_nnz == x_nnz && mp == xp;
-      if (mask_is_x) {
-        mask_ptr_dev = d_xp.ptr;
-        mask_idx_dev = d_xi.ptr;
-      } else {
-        d_mp.upload(mp, s);
-        d_mi.upload(mask_indices, static_cast<size_t>(m_nnz), s);
-        mask_ptr_dev = d_mp.ptr;
-        mask_idx_dev = d_mi.ptr;
-      }
-    }
-    // blocks of users whose dense float64 scores fit 4 GB; every cutoff ranks the same block.  (A block ends
-    // with a read-back of its metrics and item counts: ~0.7 ms of launches, synchronisation and host merge.
-    // All 138,493 users of the ML-20M shape, 29.6 GB of scores: 1 GB blocks 59.8 ms, 2 GB 50.1, 4 GB 44.5,
-    // 8 GB 42.6, one block 40.5 - against 90 / 190 / 310 ms for the first call's allocation at 1 / 4 / 8 GB.)
-    int64_t per = std::max<int64_t>(1, std::min<int64_t>(rows, (int64_t(1) << 32) / std::max<int64_t>(8 * ni, 1)));
-    if (const char *v = std::getenv("IRSPACK_AMD_EVAL_SIM_BLOCK_ROWS"))  // (tests: several blocks on a small call)
-      per = std::max<int64_t>(1, std::min<int64_t>(per, std::atoll(v)));
-    const int32_t n_tiles = static_cast<int32_t>(ceil_div(std::max<int64_t>(ni, 1), SIM_TILE));
-    // per cutoff: the running totals of the blocks, on the device (read back once, after the last block)
-    const size_t nc_ = static_cast<size_t>(std::max(n_cutoffs, 1));
-    DeviceBuffer<irs_metrics> tot_m;
-    DeviceBuffer<unsigned long long> tot_cnt;
-    tot_m.alloc(nc_);
-    tot_cnt.alloc(nc_ * static_cast<size_t>(std::max<int64_t>(ni, 1)));
-    tot_m.zero(s);
-    tot_cnt.zero(s);
-    std::fill(item_cnt, item_cnt + static_cast<int64_t>(std::max(n_cutoffs, 0)) * ni, int64_t(0));
+    CallMask mask;  // (stray columns: the kernel skips them)
+    mask.upload_or_alias(mask_indptr, mask_indices, rows, ni, x, x_indices, d_xp, d_xi, s);
+    // blocks of users whose dense float64 scores fit 4 GB; every cutoff ranks the same block.  (All 138,493 users
+    // of the ML-20M shape, 29.6 GB of scores: 1 GB blocks 59.8 ms, 2 GB 50.1, 4 GB 44.5, 8 GB 42.6, one block
+    // 40.5 - against 90 / 190 / 310 ms for the first call's allocation at 1 / 4 / 8 GB.)
+    const int64_t per = rows_per_f64_block(ni, rows, false);
+    const int32_t n_tiles = sim_tiles(ni);
+    CutoffTotals totals(CutoffTotals::BLOCKS, n_cutoffs, ni, item_cnt, s);
     if (rows > 0) e->score_buf.alloc(static_cast<size_t>(per) * ni * 8);
     DeviceBuffer<int32_t> d_wt;
-    if (w_tiled && rows > 0 && np_ > 0) {
-      const int64_t n_tp = np_ * (n_tiles + 1);
-      d_wt.alloc(static_cast<size_t>(n_tp));
-      hipLaunchKernelGGL(sim_tile_ptr_kernel, dim3(static_cast<unsigned>(ceil_div(n_tp, 256))), dim3(256), 0, s,
-                         static_cast<const int64_t *>(d_wp.ptr), static_cast<const int32_t *>(d_wi.ptr), np_, n_tiles,
-                         d_wt.ptr);
-    }
-    // launch order inside every block: rows by stored profile length, longest first (counting sort, stable)
+    if (w_tiled && rows > 0 && np_ > 0) build_tile_table(d_wt, d_wp, d_wi, np_, n_tiles, s);
     DeviceBuffer<int32_t> d_order;
     if (rows > 0) {
-      std::vector<int32_t> order(static_cast<size_t>(rows));
-      constexpr int64_t CAP = 1 << 16;
-      std::vector<int32_t> start(CAP + 2);
-      for (int64_t b = 0; b < rows; b += per) {
-        const int64_t m = std::min(per, rows - b);
-        std::fill(start.begin(), start.end(), 0);
-        auto len = [&](int64_t r) { return std::min<int64_t>(CAP, xp[b + r + 1] - xp[b + r]); };
-        for (int64_t r = 0; r < m; r++) start[CAP - len(r) + 1]++;
-        for (size_t i = 1; i < start.size(); i++) start[i] += start[i - 1];
-        for (int64_t r = 0; r < m; r++) order[b + start[CAP - len(r)]++] = static_cast<int32_t>(r);
-      }
+      std::vector<int32_t> order;
+      launch_order(x.ptr, rows, per, order);
       d_order.upload(order, s);
     }
+    const ProfileView xv{d_xp.ptr, d_xi.ptr, x.all_ones ? nullptr : d_xv.ptr};
+    const SparseWeightsView wv{d_wp.ptr, d_wi.ptr, d_wv.ptr, w_nnz, n_tiles, d_wt.ptr};
     for (int64_t b = 0; b < rows; b += per) {
       const int64_t m = std::min(per, rows - b);
       double *scores = reinterpret_cast<double *>(e->score_buf.ptr);
-      hipLaunchKernelGGL(d_wt.ptr ? sim_score_kernel<true> : sim_score_kernel<false>, dim3(static_cast<unsigned>(m * n_tiles)), dim3(64), 0, s,
-                         static_cast<const int64_t *>(d_xp.ptr), static_cast<const int32_t *>(d_xi.ptr),
-                         x_not_ones.load() ? static_cast<const double *>(d_xv.ptr) : static_cast<const double *>(nullptr),
-                         static_cast<const int64_t *>(d_wp.ptr), static_cast<const int32_t *>(d_wi.ptr),
-                         static_cast<const double *>(d_wv.ptr), std::max<int64_t>(w_nnz - 1, 0), b, ni, n_tiles, scores,
-                         static_cast<const int32_t *>(d_wt.ptr), static_cast<const int32_t *>(d_order.ptr) + b);
-      if (m_nnz > 0)
+      launch_sim_scores(xv, wv, b, m, ni, scores, d_order.ptr + b, s);
+      if (mask.ptr.ptr)
         hipLaunchKernelGGL(mask_block_kernel<double>, dim3(static_cast<unsigned>(m)), dim3(64), 0, s, scores, m, ni,
-                           mask_ptr_dev + b, mask_idx_dev);
+                           mask.ptr.ptr + b, mask.idx.ptr);
       IRS_HIP(hipGetLastError());
-      for (int32_t c = 0; c < n_cutoffs; c++) {
-        begin_accumulate(e, s);
-        rank_block<double>(e, scores, m, cutoffs[c], offset + b, recall_with_cutoff != 0, s);
-        // Metrics::merge of the block into the cutoff's totals, block after block (evaluator.cpp:76-85)
-        hipLaunchKernelGGL(metrics_fold_kernel, dim3(1), dim3(64), 0, s, static_cast<const irs_metrics *>(e->metrics.ptr),
-                           tot_m.ptr + c);
-        if (ni > 0)
-          hipLaunchKernelGGL(counts_fold_kernel, dim3(static_cast<unsigned>(ceil_div(ni, 256))), dim3(256), 0, s,
-                             static_cast<const unsigned long long *>(e->item_cnt.ptr), ni, tot_cnt.ptr + static_cast<size_t>(c) * ni);
-      }
+      totals.add_block<double>(e, scores, m, n_cutoffs, cutoffs, offset + b, recall_with_cutoff != 0, s);
     }
-    if (e->span_open) IRS_HIP(hipEventRecord(e->ev_last, s));
-    if (n_cutoffs > 0) {
-      IRS_HIP(hipMemcpyAsync(out, tot_m.ptr, sizeof(irs_metrics) * static_cast<size_t>(n_cutoffs), hipMemcpyDeviceToHost, s));
-      if (ni > 0)
-        IRS_HIP(hipMemcpyAsync(item_cnt, tot_cnt.ptr, sizeof(int64_t) * static_cast<size_t>(n_cutoffs) * ni,
-                               hipMemcpyDeviceToHost, s));
-    }
-    IRS_HIP(hipStreamSynchronize(s));
+    totals.finish(e, n_cutoffs, out, item_cnt, s);
   });
 }
 
@@ -2391,21 +2236,11 @@ irs_status irs_eval_get_metrics_dense_similarity(irs_evaluator *e, int64_t begin
     const int64_t rows = end - begin, ni = e->n_items, np_ = n_profile_cols;
     for (int32_t c = 0; c < n_cutoffs; c++) validate_call(e, rows, cutoffs[c], offset, 1);
     check_arg(np_ >= 0 && np_ < (int64_t(1) << 31), "bad profile width.");
-    check_arg(x_indptr[0] == 0, "malformed indptr.");
-    for (int64_t r = begin; r < end; r++) check_arg(x_indptr[r + 1] >= x_indptr[r], "malformed indptr.");
-    const int64_t xq0 = x_indptr[begin], x_nnz = x_indptr[end] - xq0;
-    check_arg(x_nnz == 0 || (x_indices && x_data), "null argument.");
-    check_arg(np_ == 0 || ni == 0 || w != nullptr, "null argument.");
-    std::atomic<int> bad(0);
-    parallel_ranges(x_nnz, [&](int64_t lo, int64_t hi) {
-      int32_t mn = 0, mx = 0;
-      for (int64_t q = lo; q < hi; q++) {
-        mn = std::min(mn, x_indices[xq0 + q]);
-        mx = std::max(mx, x_indices[xq0 + q]);
-      }
-      if (hi > lo && (mn < 0 || mx >= np_)) bad.store(1);
-    });
-    check_arg(bad.load() == 0, "column index out of range.");
+    ProfileRows x;
+    x.take_pointers(x_indptr, begin, end, false);
+    const int64_t x_nnz = x.nnz;
+    check_arg((x_nnz == 0 || (x_indices && x_data)) && (np_ == 0 || ni == 0 || w != nullptr), "null argument.");
+    x.scan_entries(x_indices, x_data, np_, false);
     IRS_HIP(hipSetDevice(e->device));
     hipStream_t s = nullptr;
     PhaseClock clock(s);
@@ -2415,59 +2250,33 @@ irs_status irs_eval_get_metrics_dense_similarity(irs_evaluator *e, int64_t begin
     DeviceBuffer<int32_t> d_xi;
     DeviceBuffer<double> d_xv;
     DeviceBuffer<char> d_w;
-    std::vector<int64_t> xp(static_cast<size_t>(rows) + 1);
-    for (int64_t r = 0; r <= rows; r++) xp[r] = x_indptr[begin + r] - xq0;
-    d_xp.upload(xp, s);
-    d_xi.upload(x_indices + xq0, static_cast<size_t>(x_nnz), s);
-    d_xv.upload(x_data + xq0, static_cast<size_t>(x_nnz), s);
+    d_xp.upload(x.ptr, s);
+    d_xi.upload(x_indices + x.first, static_cast<size_t>(x_nnz), s);
+    d_xv.upload(x_data + x.first, static_cast<size_t>(x_nnz), s);
     if (rows > 0 && x_nnz > 0)
       d_w.upload(static_cast<const char *>(w), static_cast<size_t>(np_) * ni * (w_is_f64 ? 8 : 4), s);
     CallMask mask;
-    mask.upload(mask_indptr, mask_indices, rows, ni, s);
-    // blocks of users whose float64 scores fit 4 GB, as in irs_eval_get_metrics_similarity
-    int64_t per = std::max<int64_t>(1, std::min<int64_t>(rows, (int64_t(1) << 32) / std::max<int64_t>(8 * ni, 1)));
-    if (per < rows && per >= HOST_LOOP_ROWS) per = per / HOST_LOOP_ROWS * HOST_LOOP_ROWS;  // (whole chunks of the host loop)
-    if (const char *v = std::getenv("IRSPACK_AMD_EVAL_SIM_BLOCK_ROWS"))  // (tests: several blocks on a small call)
-      per = std::max<int64_t>(1, std::min<int64_t>(per, std::atoll(v)));
+    mask.upload(mask_indptr, mask_indices, rows, ni, true, s);
+    const int64_t per = rows_per_f64_block(ni, rows, true);  // (whole chunks of the host loop)
     const int64_t n_strips = ceil_div(std::max<int64_t>(ni, 1), DS_STRIP);
     check_arg(per * n_strips < (int64_t(1) << 31), "score block too large for one launch.");
-    CutoffTotals totals;
-    totals.begin(n_cutoffs, ni, s);
-    std::fill(item_cnt, item_cnt + static_cast<int64_t>(std::max(n_cutoffs, 0)) * ni, int64_t(0));
-    // launch order inside every block: rows by stored profile length, longest first (counting sort, stable)
+    CutoffTotals totals(CutoffTotals::CHUNKS, n_cutoffs, ni, item_cnt, s);
     DeviceBuffer<int32_t> d_order;
     if (rows > 0 && ni > 0) {
       e->score_buf.alloc(static_cast<size_t>(per) * ni * 8);
-      std::vector<int32_t> order(static_cast<size_t>(rows));
-      constexpr int64_t CAP = 1 << 16;
-      std::vector<int32_t> start(CAP + 2);
-      for (int64_t b = 0; b < rows; b += per) {
-        const int64_t m = std::min(per, rows - b);
-        std::fill(start.begin(), start.end(), 0);
-        auto len = [&](int64_t r) { return std::min<int64_t>(CAP, xp[b + r + 1] - xp[b + r]); };
-        for (int64_t r = 0; r < m; r++) start[CAP - len(r) + 1]++;
-        for (size_t i = 1; i < start.size(); i++) start[i] += start[i - 1];
-        for (int64_t r = 0; r < m; r++) order[b + start[CAP - len(r)]++] = static_cast<int32_t>(r);
-      }
+      std::vector<int32_t> order;
+      launch_order(x.ptr, rows, per, order);
       d_order.upload(order, s);
     }
     clock.mark(PH_UPLOAD);
+    const ProfileView xv{d_xp.ptr, d_xi.ptr, d_xv.ptr};
     for (int64_t b = 0; b < rows && ni > 0; b += per) {
       const int64_t m = std::min(per, rows - b);
       double *scores = reinterpret_cast<double *>(e->score_buf.ptr);
-      const dim3 grid(static_cast<unsigned>(m * n_strips));
       if (x_nnz == 0)  // (no profile entry in the whole call: W was not uploaded, every score is 0)
         IRS_HIP(hipMemsetAsync(scores, 0, static_cast<size_t>(m) * ni * 8, s));
-      else if (w_is_f64)
-        hipLaunchKernelGGL(dense_sim_score_kernel<double>, grid, dim3(64), 0, s, static_cast<const int64_t *>(d_xp.ptr),
-                           static_cast<const int32_t *>(d_xi.ptr), static_cast<const double *>(d_xv.ptr),
-                           reinterpret_cast<const double *>(d_w.ptr), b, m, ni, scores,
-                           static_cast<const int32_t *>(d_order.ptr) + b);
       else
-        hipLaunchKernelGGL(dense_sim_score_kernel<float>, grid, dim3(64), 0, s, static_cast<const int64_t *>(d_xp.ptr),
-                           static_cast<const int32_t *>(d_xi.ptr), static_cast<const double *>(d_xv.ptr),
-                           reinterpret_cast<const float *>(d_w.ptr), b, m, ni, scores,
-                           static_cast<const int32_t *>(d_order.ptr) + b);
+        launch_dense_scores(xv, d_w.ptr, w_is_f64 != 0, b, m, ni, scores, d_order.ptr + b, s);
       IRS_HIP(hipGetLastError());
       clock.mark(PH_SCORE);
       if (mask.ptr.ptr)
@@ -2478,7 +2287,7 @@ irs_status irs_eval_get_metrics_dense_similarity(irs_evaluator *e, int64_t begin
       totals.add_block<double>(e, scores, m, n_cutoffs, cutoffs, offset + b, recall_with_cutoff != 0, s);
       clock.mark(PH_RANK);
     }
-    totals.finish(n_cutoffs, ni, out, item_cnt, s);
+    totals.finish(e, n_cutoffs, out, item_cnt, s);
     clock.read(e->phase_ms);
   });
 }
@@ -2499,29 +2308,16 @@ irs_status irs_eval_get_metrics_factors(irs_evaluator *e, int64_t begin, int64_t
     IRS_HIP(hipSetDevice(e->device));
     hipStream_t s = nullptr;
     PhaseClock clock(s);
-    // the factor tables, rows zero-padded to KP (a multiple of 32) on the way up: what the MFMA tiles read
+    // the factor tables, rows zero-padded to KP (a multiple of 32) on the way up
     const int32_t KP = (k + 31) / 32 * 32;
     DeviceBuffer<float> d_user, d_item;
-    auto upload_padded = [&](DeviceBuffer<float> &d, const float *host, int64_t n) {
-      d.alloc(static_cast<size_t>(std::max<int64_t>(n, 1)) * KP);
-      d.zero(s);
-      if (n > 0)
-        IRS_HIP(hipMemcpy2DAsync(d.ptr, sizeof(float) * KP, host, sizeof(float) * k, sizeof(float) * k,
-                                 static_cast<size_t>(n), hipMemcpyHostToDevice, s));
-    };
-    upload_padded(d_user, rows > 0 ? user_factors + begin * static_cast<int64_t>(k) : nullptr, rows);
-    upload_padded(d_item, item_factors, ni);
+    upload_padded(d_user, rows > 0 ? user_factors + begin * static_cast<int64_t>(k) : nullptr, rows, k, KP, s);
+    upload_padded(d_item, item_factors, ni, k, KP, s);
     CallMask mask;
-    mask.upload(mask_indptr, mask_indices, rows, ni, s);
-    // users scored and ranked per pass: as in irs_eval_get_metrics_ials
-    const int64_t fit = (int64_t(1) << 31) / (std::max<int64_t>(ni, 1) * 4);
-    int64_t block_cap = 16384;
-    if (const char *eb = std::getenv("IRSPACK_AMD_EVAL_BLOCK"))
-      block_cap = std::max<int64_t>(256, std::atoll(eb) / HOST_LOOP_ROWS * HOST_LOOP_ROWS);
-    const int64_t BLOCK = std::min<int64_t>(block_cap, std::max<int64_t>(1024, fit / 1024 * 1024));
-    CutoffTotals totals;
-    totals.begin(n_cutoffs, ni, s);
-    std::fill(item_cnt, item_cnt + static_cast<int64_t>(std::max(n_cutoffs, 0)) * ni, int64_t(0));
+    mask.upload(mask_indptr, mask_indices, rows, ni, true, s);
+    // users scored and ranked per pass: as in irs_eval_get_metrics_ials, in whole chunks of the host loop
+    const int64_t BLOCK = rows_per_f32_block(ni, "IRSPACK_AMD_EVAL_BLOCK", true, 1024);
+    CutoffTotals totals(CutoffTotals::CHUNKS, n_cutoffs, ni, item_cnt, s);
     DeviceBuffer<float> &scores = e->fused_scores;
     if (rows > 0 && ni > 0) scores.alloc(static_cast<size_t>(std::min(BLOCK, rows)) * ni);
     clock.mark(PH_UPLOAD);
@@ -2539,7 +2335,7 @@ irs_status irs_eval_get_metrics_factors(irs_evaluator *e, int64_t begin, int64_t
       totals.add_block<float>(e, scores.ptr, m, n_cutoffs, cutoffs, offset + b, recall_with_cutoff != 0, s);
       clock.mark(PH_RANK);
     }
-    totals.finish(n_cutoffs, ni, out, item_cnt, s);
+    totals.finish(e, n_cutoffs, out, item_cnt, s);
     clock.read(e->phase_ms);
   });
 }
@@ -2564,10 +2360,7 @@ irs_status irs_eval_get_metrics_ials(irs_evaluator *e, irs_ials_trainer *t, int6
     IRS_HIP(hipSetDevice(e->device));
     // users scored and ranked per pass: enough rows to fill the device with one wave per row
     // (32 waves x 256 CUs), within a 2 GiB score block
-    const int64_t fit = (int64_t(1) << 31) / (std::max<int64_t>(e->n_items, 1) * 4);
-    int64_t block_cap = 16384;
-    if (const char *eb = std::getenv("IRSPACK_AMD_EVAL_BLOCK")) block_cap = std::max<int64_t>(256, std::atoll(eb));
-    const int64_t BLOCK = std::min<int64_t>(block_cap, std::max<int64_t>(1024, fit / 1024 * 1024));
+    const int64_t BLOCK = rows_per_f32_block(e->n_items, "IRSPACK_AMD_EVAL_BLOCK", false, 1024);
     DeviceBuffer<int64_t> mptr;
     DeviceBuffer<int32_t> midx;
     void *sv = nullptr;
@@ -2727,25 +2520,15 @@ irs_status irs_retrieve_recommend(int32_t is_f64, const void *scores, int64_t ro
     if (rows == 0 || cutoff <= 0) return;
     require_device(device);
     hipStream_t s = nullptr;
-    // candidate lists keep their order and duplicates; out-of-range ids are dropped (:468-472)
-    std::vector<int64_t> lptr(n_lists + 1, 0);
-    std::vector<int32_t> litems;
-    int64_t max_cand = n_lists == 0 ? n_items : 0;
-    for (int64_t l = 0; l < n_lists; l++) {
-      for (int64_t q = list_ptr[l]; q < list_ptr[l + 1]; q++)
-        if (list_items[q] >= 0 && list_items[q] < n_items)
-          litems.push_back(static_cast<int32_t>(list_items[q]));
-      lptr[l + 1] = static_cast<int64_t>(litems.size());
-      max_cand = std::max(max_cand, lptr[l + 1] - lptr[l]);
-    }
+    CandidateLists lists;
+    lists.take(n_lists, list_ptr, list_items, n_items, false);
     DeviceBuffer<int64_t> d_lptr;
     DeviceBuffer<int32_t> d_litems, d_rec;
     DeviceBuffer<RowOut> d_rows;
     DeviceBuffer<char> d_scores;
     if (n_lists > 0) {
-      d_lptr.upload(lptr, s);
-      if (litems.empty()) litems.push_back(0);
-      d_litems.upload(litems, s);
+      d_lptr.upload(lists.ptr, s);
+      d_litems.upload(lists.items, s);
     }
     const size_t bytes = static_cast<size_t>(rows) * n_items * (is_f64 ? 8 : 4);
     d_scores.alloc(std::max<size_t>(bytes, 8));
@@ -2754,22 +2537,12 @@ irs_status irs_retrieve_recommend(int32_t is_f64, const void *scores, int64_t ro
     d_rows.alloc(rows);
     DeviceBuffer<int32_t> d_todo;
     d_todo.alloc(rows);
-    EvalParams p{};
-    p.scores = d_scores.ptr;
-    p.rows = rows;
-    p.n_items = n_items;
-    p.offset = 0;
-    p.rec_mode = n_lists == 0 ? 0 : (n_lists == 1 ? 1 : 2);
-    p.rec_ptr = d_lptr.ptr;
-    p.rec_items = d_litems.ptr;
-    p.cutoff = static_cast<int32_t>(cutoff);
-    p.retrieve = 1;
-    p.out = d_rows.ptr;
-    p.rec_out = d_rec.ptr;
+    const EvalParams p = retrieve_params(d_scores.ptr, rows, n_items, 0, n_lists, d_lptr.ptr, d_litems.ptr, cutoff,
+                                         d_rows.ptr, d_rec.ptr);
     if (is_f64)
-      launch_rank<double>(p, max_cand, s, d_todo.ptr);
+      launch_rank<double>(p, lists.max_cand, s, d_todo.ptr);
     else
-      launch_rank<float>(p, max_cand, s, d_todo.ptr);
+      launch_rank<float>(p, lists.max_cand, s, d_todo.ptr);
     IRS_HIP(hipGetLastError());
     IRS_HIP(hipMemcpyAsync(out_idx, d_rec.ptr, static_cast<size_t>(rows) * cutoff * sizeof(int32_t),
                            hipMemcpyDeviceToHost, s));
@@ -2779,403 +2552,4 @@ irs_status irs_retrieve_recommend(int32_t is_f64, const void *scores, int64_t ro
 
 }  // extern "C"
 
-// ---------------------------------------------------------------------------------------------------------
-// Serving: irs_serve_* (include/irspack_amd.h).  The item-side operand lives in an irs_server; a recommend call
-// uploads its rows, then per chunk: score, mask, rank (retrieve = 1), emit (serve_kernels.hpp).
-namespace {
-
-// what the two recommend calls share
-struct ServeCall {
-  int64_t rows;
-  const int64_t *excl_indptr;
-  const int32_t *excl_indices;
-  int64_t n_lists;
-  const int64_t *list_ptr;
-  const int64_t *list_items;
-  int64_t cutoff;
-  int32_t *out_idx;
-  float *out_score;
-  int32_t *out_len;
-  // filled by serve_check
-  int32_t width = 0;
-  int64_t excl_nnz = 0, max_cand = 0;
-  std::vector<int64_t> excl_ptr_host, list_ptr_host;
-  std::vector<int32_t> list_items_host;
-};
-
-// rows per chunk: as irs_eval_get_metrics_factors sizes its blocks (a 2 GiB float block - the same rows of
-// float64 scores are the 4 GB of irs_eval_get_metrics_similarity -, at most 16384 rows)
-int64_t serve_block_rows(int64_t ni) {
-  const int64_t fit = (int64_t(1) << 31) / (std::max<int64_t>(ni, 1) * 4);
-  int64_t block_cap = 16384;
-  if (const char *eb = std::getenv("IRSPACK_AMD_SERVE_BLOCK")) block_cap = std::max<int64_t>(256, std::atoll(eb));
-  return std::min<int64_t>(block_cap, std::max<int64_t>(1, fit >= 1024 ? fit / 1024 * 1024 : fit));
-}
-
-// every argument check of what the two calls share (host only); false: nothing to compute (the outputs are set)
-bool serve_check(irs_server *sv, ServeCall &c) {
-  check_arg(c.rows >= 0, "negative row count.");
-  check_arg(c.cutoff >= 0, "cutoff must not be negative.");
-  check_arg(c.n_lists == 0 || c.n_lists == 1 || c.n_lists == c.rows,
-            "allowed_indices, if not empty, must have a size equal to X.rows()");
-  check_arg(c.n_lists == 0 || c.list_ptr != nullptr, "null argument.");
-  const int64_t ni = sv->n_items;
-  c.width = static_cast<int32_t>(std::min<int64_t>(c.cutoff, ni));
-  check_arg(c.rows == 0 || c.out_len != nullptr, "null argument.");
-  check_arg(c.rows == 0 || c.width == 0 || (c.out_idx && c.out_score), "null argument.");
-  check_arg(c.rows * static_cast<int64_t>(std::max(c.width, 1)) < (int64_t(1) << 40), "output too large.");
-  // exclusion rows: pointers that do not decrease, columns inside [0, n_items); rebased to 0
-  c.excl_nnz = c.excl_indptr && c.rows > 0 ? c.excl_indptr[c.rows] - c.excl_indptr[0] : 0;
-  if (c.excl_indptr && c.rows > 0) {
-    check_arg(c.excl_indptr[0] >= 0, "excl_indptr must not be negative.");
-    c.excl_ptr_host.resize(static_cast<size_t>(c.rows) + 1);
-    for (int64_t r = 0; r <= c.rows; r++) {
-      c.excl_ptr_host[r] = c.excl_indptr[r] - c.excl_indptr[0];
-      check_arg(c.excl_ptr_host[r] >= (r ? c.excl_ptr_host[r - 1] : 0), "excl_indptr must not decrease.");
-    }
-    check_arg(c.excl_nnz == 0 || c.excl_indices != nullptr, "excl_indices is null.");
-    std::atomic<int> bad(0);
-    const int32_t *ei = c.excl_indices;
-    parallel_ranges(c.excl_nnz, [&](int64_t lo, int64_t hi) {
-      int32_t mn = 0, mx = 0;
-      for (int64_t q = lo; q < hi; q++) {
-        mn = std::min(mn, ei[q]);
-        mx = std::max(mx, ei[q]);
-      }
-      if (hi > lo && (mn < 0 || mx >= ni)) bad.store(1);
-    });
-    check_arg(bad.load() == 0, "excluded item index out of range.");
-  }
-  // candidate lists keep their order and duplicates; out-of-range ids are dropped (util.hpp:468-472)
-  c.list_ptr_host.assign(static_cast<size_t>(c.n_lists) + 1, 0);
-  c.max_cand = c.n_lists == 0 ? ni : 0;
-  check_arg(c.n_lists == 0 || c.list_ptr[0] >= 0, "list_ptr must not be negative.");
-  for (int64_t l = 0; l < c.n_lists; l++) {
-    check_arg(c.list_ptr[l + 1] >= c.list_ptr[l], "list_ptr must not decrease.");
-    check_arg(c.list_ptr[l + 1] == c.list_ptr[l] || c.list_items != nullptr, "null argument.");
-    for (int64_t q = c.list_ptr[l]; q < c.list_ptr[l + 1]; q++)
-      if (c.list_items[q] >= 0 && c.list_items[q] < ni) c.list_items_host.push_back(static_cast<int32_t>(c.list_items[q]));
-    c.list_ptr_host[l + 1] = static_cast<int64_t>(c.list_items_host.size());
-    c.max_cand = std::max(c.max_cand, c.list_ptr_host[l + 1] - c.list_ptr_host[l]);
-  }
-  check_arg(static_cast<int64_t>(c.list_items_host.size()) < (int64_t(1) << 31), "allowed lists too long.");
-  if (c.rows == 0) return false;
-  if (c.width == 0) {
-    std::fill(c.out_len, c.out_len + c.rows, 0);
-    return false;
-  }
-  return true;
-}
-
-// The chunks of a call: `score(b, m, block)` leaves the scores of the rows b .. b + m in `block`; then the
-// exclusions, the ranking and the output stage; three copies home after the last chunk.
-template <class T, class ScoreFn>
-void serve_run(irs_server *sv, ServeCall &c, hipStream_t s, PhaseClock &clock, ScoreFn &&score) {
-  const int64_t ni = sv->n_items, rows = c.rows, width = c.width;
-  if (c.excl_nnz > 0) {
-    sv->excl_ptr.upload(c.excl_ptr_host, s);
-    sv->excl_idx.upload(c.excl_indices, static_cast<size_t>(c.excl_nnz), s);
-  }
-  if (c.n_lists > 0) {
-    sv->list_ptr.upload(c.list_ptr_host, s);
-    if (c.list_items_host.empty()) c.list_items_host.push_back(0);
-    sv->list_items.upload(c.list_items_host, s);
-  }
-  const int64_t BLOCK = std::min(serve_block_rows(ni), rows);
-  sv->scores.alloc(static_cast<size_t>(BLOCK) * ni * sizeof(T));
-  sv->rec.alloc(static_cast<size_t>(BLOCK) * width);
-  sv->todo.alloc(static_cast<size_t>(BLOCK));
-  sv->row_out.alloc(static_cast<size_t>(BLOCK));
-  sv->out_idx.alloc(static_cast<size_t>(rows) * width);
-  sv->out_score.alloc(static_cast<size_t>(rows) * width);
-  sv->out_len.alloc(static_cast<size_t>(rows));
-  clock.mark(PH_UPLOAD);
-  T *block = reinterpret_cast<T *>(sv->scores.ptr);
-  for (int64_t b = 0; b < rows; b += BLOCK) {
-    const int64_t m = std::min(BLOCK, rows - b);
-    score(b, m, block);
-    IRS_HIP(hipGetLastError());
-    clock.mark(PH_SCORE);
-    if (c.excl_nnz > 0)
-      hipLaunchKernelGGL(mask_block_kernel<T>, dim3(static_cast<unsigned>(m)), dim3(64), 0, s, block, m, ni,
-                         static_cast<const int64_t *>(sv->excl_ptr.ptr) + b, static_cast<const int32_t *>(sv->excl_idx.ptr));
-    IRS_HIP(hipGetLastError());
-    clock.mark(PH_MASK);
-    EvalParams p{};
-    p.scores = block;
-    p.rows = m;
-    p.n_items = ni;
-    p.offset = b;  // (per-row lists are numbered by the call's rows)
-    p.rec_mode = c.n_lists == 0 ? 0 : (c.n_lists == 1 ? 1 : 2);
-    p.rec_ptr = sv->list_ptr.ptr;
-    p.rec_items = sv->list_items.ptr;
-    p.cutoff = static_cast<int32_t>(width);
-    p.retrieve = 1;
-    p.out = sv->row_out.ptr;
-    p.rec_out = sv->rec.ptr;
-    if (c.n_lists > 0)  // (equal scores in candidate order, whatever the order of the list)
-      launch_rank<T, true>(p, c.max_cand, s, sv->todo.ptr);
-    else
-      launch_rank<T>(p, c.max_cand, s, sv->todo.ptr);
-    hipLaunchKernelGGL(serve_emit_kernel<T>, dim3(static_cast<unsigned>(ceil_div(m, 4))), dim3(256), 0, s,
-                       static_cast<const int32_t *>(sv->rec.ptr), static_cast<const T *>(block), m, ni,
-                       static_cast<int32_t>(width), sv->out_idx.ptr + b * width, sv->out_score.ptr + b * width,
-                       sv->out_len.ptr + b);
-    IRS_HIP(hipGetLastError());
-    clock.mark(PH_RANK);
-  }
-  IRS_HIP(hipMemcpyAsync(c.out_idx, sv->out_idx.ptr, static_cast<size_t>(rows) * width * sizeof(int32_t),
-                         hipMemcpyDeviceToHost, s));
-  IRS_HIP(hipMemcpyAsync(c.out_score, sv->out_score.ptr, static_cast<size_t>(rows) * width * sizeof(float),
-                         hipMemcpyDeviceToHost, s));
-  IRS_HIP(hipMemcpyAsync(c.out_len, sv->out_len.ptr, static_cast<size_t>(rows) * sizeof(int32_t),
-                         hipMemcpyDeviceToHost, s));
-  clock.mark(PH_RANK);
-  IRS_HIP(hipStreamSynchronize(s));
-  clock.read(sv->phase_ms);
-}
-
-}  // namespace
-
-extern "C" {
-
-irs_status irs_serve_create_similarity(int64_t n_profile_cols, int64_t n_items, const int64_t *w_indptr,
-                                       const int32_t *w_indices, const double *w_data, int32_t device,
-                                       irs_server **out) {
-  return guard([&] {
-    check_arg(out && w_indptr, "null argument.");
-    const int64_t np_ = n_profile_cols, ni = n_items;
-    check_arg(np_ >= 0 && np_ < (int64_t(1) << 31) && ni >= 0 && ni < (int64_t(1) << 31), "bad shape.");
-    check_arg(w_indptr[0] == 0, "malformed indptr.");
-    for (int64_t i = 0; i < np_; i++) check_arg(w_indptr[i + 1] >= w_indptr[i], "malformed indptr.");
-    const int64_t w_nnz = w_indptr[np_];
-    check_arg(w_nnz == 0 || (w_indices && w_data), "null argument.");
-    // columns in range; a column stored twice in a row is refused (two lanes of sim_score_kernel would add to
-    // one sum at the same time); rows with increasing columns are cut into per-tile ranges
-    std::atomic<int> bad(0), dup(0), unsorted(0);
-    parallel_ranges(np_, [&](int64_t lo, int64_t hi) {
-      std::vector<int32_t> tmp;
-      for (int64_t r = lo; r < hi; r++) {
-        bool inc = true;
-        for (int64_t q = w_indptr[r]; q < w_indptr[r + 1]; q++) {
-          if (w_indices[q] < 0 || w_indices[q] >= ni) bad.store(1);
-          if (q > w_indptr[r] && w_indices[q] <= w_indices[q - 1]) inc = false;
-        }
-        if (!inc) {
-          unsorted.store(1);
-          tmp.assign(w_indices + w_indptr[r], w_indices + w_indptr[r + 1]);
-          std::sort(tmp.begin(), tmp.end());
-          if (std::adjacent_find(tmp.begin(), tmp.end()) != tmp.end()) dup.store(1);
-        }
-      }
-    }, 16, 4096);
-    check_arg(bad.load() == 0, "column index out of range.");
-    check_arg(dup.load() == 0, "duplicate column in a row of W");
-    require_device(device);
-    auto sv = std::make_unique<irs_server>();
-    sv->kind = irs_server::SPARSE;
-    sv->device = device;
-    sv->n_profile_cols = np_;
-    sv->n_items = ni;
-    sv->w_nnz = w_nnz;
-    sv->n_tiles = static_cast<int32_t>(ceil_div(std::max<int64_t>(ni, 1), SIM_TILE));
-    sv->w_tiled = unsorted.load() == 0 && w_nnz < (int64_t(1) << 31) && np_ > 0;
-    hipStream_t s = nullptr;
-    sv->w_ptr.upload(w_indptr, static_cast<size_t>(np_) + 1, s);
-    sv->w_idx.upload(w_indices, static_cast<size_t>(w_nnz), s);
-    sv->w_val.upload(w_data, static_cast<size_t>(w_nnz), s);
-    if (sv->w_tiled) {
-      const int64_t n_tp = np_ * (sv->n_tiles + 1);
-      sv->w_tptr.alloc(static_cast<size_t>(n_tp));
-      hipLaunchKernelGGL(sim_tile_ptr_kernel, dim3(static_cast<unsigned>(ceil_div(n_tp, 256))), dim3(256), 0, s,
-                         static_cast<const int64_t *>(sv->w_ptr.ptr), static_cast<const int32_t *>(sv->w_idx.ptr), np_,
-                         sv->n_tiles, sv->w_tptr.ptr);
-      IRS_HIP(hipGetLastError());
-    }
-    IRS_HIP(hipStreamSynchronize(s));
-    *out = sv.release();
-  });
-}
-
-irs_status irs_serve_create_dense_similarity(int64_t n_profile_cols, int64_t n_items, int32_t w_is_f64, const void *w,
-                                             int32_t device, irs_server **out) {
-  return guard([&] {
-    check_arg(out != nullptr, "null argument.");
-    const int64_t np_ = n_profile_cols, ni = n_items;
-    check_arg(np_ >= 0 && np_ < (int64_t(1) << 31) && ni >= 0 && ni < (int64_t(1) << 31), "bad shape.");
-    check_arg(np_ == 0 || ni == 0 || w != nullptr, "null argument.");
-    require_device(device);
-    auto sv = std::make_unique<irs_server>();
-    sv->kind = irs_server::DENSE;
-    sv->device = device;
-    sv->n_profile_cols = np_;
-    sv->n_items = ni;
-    sv->w_is_f64 = w_is_f64 ? 1 : 0;
-    hipStream_t s = nullptr;
-    if (np_ > 0 && ni > 0)
-      sv->w_dense.upload(static_cast<const char *>(w), static_cast<size_t>(np_) * ni * (w_is_f64 ? 8 : 4), s);
-    IRS_HIP(hipStreamSynchronize(s));
-    *out = sv.release();
-  });
-}
-
-irs_status irs_serve_create_factors(int64_t n_items, int32_t k, const float *item_factors, int32_t device,
-                                    irs_server **out) {
-  return guard([&] {
-    check_arg(out != nullptr, "null argument.");
-    check_arg(k >= 1 && k <= 576, "the number of factors must lie in 1 .. 576.");
-    check_arg(n_items >= 0 && n_items < (int64_t(1) << 31), "bad shape.");
-    check_arg(n_items == 0 || item_factors != nullptr, "null argument.");
-    require_device(device);
-    auto sv = std::make_unique<irs_server>();
-    sv->kind = irs_server::FACTORS;
-    sv->device = device;
-    sv->n_items = n_items;
-    sv->k = k;
-    sv->KP = (k + 31) / 32 * 32;
-    hipStream_t s = nullptr;
-    sv->item.alloc(static_cast<size_t>(std::max<int64_t>(n_items, 1)) * sv->KP);
-    sv->item.zero(s);
-    if (n_items > 0)
-      IRS_HIP(hipMemcpy2DAsync(sv->item.ptr, sizeof(float) * sv->KP, item_factors, sizeof(float) * k, sizeof(float) * k,
-                               static_cast<size_t>(n_items), hipMemcpyHostToDevice, s));
-    IRS_HIP(hipStreamSynchronize(s));
-    *out = sv.release();
-  });
-}
-
-irs_status irs_serve_destroy(irs_server *sv) {
-  return guard([&] {
-    if (sv) {
-      (void)hipSetDevice(sv->device);
-      delete sv;
-    }
-  });
-}
-
-irs_status irs_serve_last_phases(irs_server *sv, double *ms) {
-  return guard([&] {
-    check_arg(sv && ms, "null argument.");
-    std::lock_guard<std::mutex> one_call(sv->call_mutex);
-    std::copy(sv->phase_ms, sv->phase_ms + 4, ms);
-  });
-}
-
-irs_status irs_serve_recommend_profiles(irs_server *sv, int64_t rows, const int64_t *x_indptr, const int32_t *x_indices,
-                                        const double *x_data, const int64_t *excl_indptr, const int32_t *excl_indices,
-                                        int64_t n_lists, const int64_t *list_ptr, const int64_t *list_items,
-                                        int64_t cutoff, int32_t *out_idx, float *out_score, int32_t *out_len) {
-  return guard([&] {
-    check_arg(sv != nullptr, "null argument.");
-    check_arg(sv->kind == irs_server::SPARSE || sv->kind == irs_server::DENSE,
-              "this server holds factors: call irs_serve_recommend_factors.");
-    ServeCall c{rows, excl_indptr, excl_indices, n_lists, list_ptr, list_items, cutoff, out_idx, out_score, out_len};
-    check_arg(rows <= 0 || x_indptr != nullptr, "null argument.");
-    const int64_t np_ = sv->n_profile_cols, ni = sv->n_items;
-    const int64_t xq0 = rows > 0 ? x_indptr[0] : 0;
-    check_arg(xq0 >= 0, "malformed indptr.");
-    for (int64_t r = 0; r < rows; r++) check_arg(x_indptr[r + 1] >= x_indptr[r], "malformed indptr.");
-    const int64_t x_nnz = rows > 0 ? x_indptr[rows] - xq0 : 0;
-    check_arg(x_nnz == 0 || (x_indices && x_data), "null argument.");
-    check_arg(x_nnz < (int64_t(1) << 40), "profile too large.");
-    std::atomic<int> bad(0), x_not_ones(0);
-    parallel_ranges(x_nnz, [&](int64_t lo, int64_t hi) {
-      int32_t mn = 0, mx = 0;
-      uint64_t diff = 0;
-      for (int64_t q = lo; q < hi; q++) {
-        mn = std::min(mn, x_indices[xq0 + q]);
-        mx = std::max(mx, x_indices[xq0 + q]);
-        uint64_t bits;
-        std::memcpy(&bits, x_data + xq0 + q, 8);
-        diff |= bits ^ 0x3ff0000000000000ull;
-      }
-      if (hi > lo && (mn < 0 || mx >= np_)) bad.store(1);
-      if (diff) x_not_ones.store(1);
-    });
-    check_arg(bad.load() == 0, "column index out of range.");
-    if (!serve_check(sv, c)) return;
-    std::lock_guard<std::mutex> one_call(sv->call_mutex);  // (the call scratch is the handle's)
-    const int64_t BLOCK = std::min(serve_block_rows(ni), rows);
-    const int64_t n_strips = ceil_div(std::max<int64_t>(ni, 1), DS_STRIP);
-    check_arg(BLOCK * std::max<int64_t>(n_strips, sv->n_tiles) < (int64_t(1) << 31), "score block too large for one launch.");
-    IRS_HIP(hipSetDevice(sv->device));
-    hipStream_t s = nullptr;
-    PhaseClock clock(s);
-    std::vector<int64_t> xp(static_cast<size_t>(rows) + 1);
-    for (int64_t r = 0; r <= rows; r++) xp[r] = x_indptr[r] - xq0;
-    sv->x_ptr.upload(xp, s);
-    sv->x_idx.upload(x_indices + xq0, static_cast<size_t>(x_nnz), s);
-    // (the sparse kernel reads no values when they are all ones; the dense one always does)
-    const bool with_values = sv->kind == irs_server::DENSE || x_not_ones.load() != 0;
-    if (with_values) sv->x_val.upload(x_data + xq0, static_cast<size_t>(x_nnz), s);
-    // launch order inside every chunk: rows by stored profile length, longest first (counting sort, stable)
-    {
-      std::vector<int32_t> order(static_cast<size_t>(rows));
-      constexpr int64_t CAP = 1 << 16;
-      std::vector<int32_t> start(CAP + 2);
-      for (int64_t b = 0; b < rows; b += BLOCK) {
-        const int64_t m = std::min(BLOCK, rows - b);
-        std::fill(start.begin(), start.end(), 0);
-        auto len = [&](int64_t r) { return std::min<int64_t>(CAP, xp[b + r + 1] - xp[b + r]); };
-        for (int64_t r = 0; r < m; r++) start[CAP - len(r) + 1]++;
-        for (size_t i = 1; i < start.size(); i++) start[i] += start[i - 1];
-        for (int64_t r = 0; r < m; r++) order[b + start[CAP - len(r)]++] = static_cast<int32_t>(r);
-      }
-      sv->order.upload(order, s);
-    }
-    serve_run<double>(sv, c, s, clock, [&](int64_t b, int64_t m, double *block) {
-      const int32_t *order = static_cast<const int32_t *>(sv->order.ptr) + b;
-      if (x_nnz == 0) {  // (no profile entry in the whole call: every score is 0)
-        IRS_HIP(hipMemsetAsync(block, 0, static_cast<size_t>(m) * ni * 8, s));
-      } else if (sv->kind == irs_server::SPARSE) {
-        hipLaunchKernelGGL(sv->w_tiled ? sim_score_kernel<true> : sim_score_kernel<false>,
-                           dim3(static_cast<unsigned>(m * sv->n_tiles)), dim3(64), 0, s,
-                           static_cast<const int64_t *>(sv->x_ptr.ptr), static_cast<const int32_t *>(sv->x_idx.ptr),
-                           with_values ? static_cast<const double *>(sv->x_val.ptr) : static_cast<const double *>(nullptr),
-                           static_cast<const int64_t *>(sv->w_ptr.ptr), static_cast<const int32_t *>(sv->w_idx.ptr),
-                           static_cast<const double *>(sv->w_val.ptr), std::max<int64_t>(sv->w_nnz - 1, 0), b, ni,
-                           sv->n_tiles, block, sv->w_tiled ? static_cast<const int32_t *>(sv->w_tptr.ptr) : nullptr, order);
-      } else if (sv->w_is_f64) {
-        hipLaunchKernelGGL(dense_sim_score_kernel<double>, dim3(static_cast<unsigned>(m * n_strips)), dim3(64), 0, s,
-                           static_cast<const int64_t *>(sv->x_ptr.ptr), static_cast<const int32_t *>(sv->x_idx.ptr),
-                           static_cast<const double *>(sv->x_val.ptr), reinterpret_cast<const double *>(sv->w_dense.ptr), b, m,
-                           ni, block, order);
-      } else {
-        hipLaunchKernelGGL(dense_sim_score_kernel<float>, dim3(static_cast<unsigned>(m * n_strips)), dim3(64), 0, s,
-                           static_cast<const int64_t *>(sv->x_ptr.ptr), static_cast<const int32_t *>(sv->x_idx.ptr),
-                           static_cast<const double *>(sv->x_val.ptr), reinterpret_cast<const float *>(sv->w_dense.ptr), b, m,
-                           ni, block, order);
-      }
-    });
-  });
-}
-
-irs_status irs_serve_recommend_factors(irs_server *sv, int64_t rows, const float *user_factors,
-                                       const int64_t *excl_indptr, const int32_t *excl_indices, int64_t n_lists,
-                                       const int64_t *list_ptr, const int64_t *list_items, int64_t cutoff,
-                                       int32_t *out_idx, float *out_score, int32_t *out_len) {
-  return guard([&] {
-    check_arg(sv != nullptr, "null argument.");
-    check_arg(sv->kind == irs_server::FACTORS, "this server holds similarity weights: call irs_serve_recommend_profiles.");
-    ServeCall c{rows, excl_indptr, excl_indices, n_lists, list_ptr, list_items, cutoff, out_idx, out_score, out_len};
-    check_arg(rows <= 0 || user_factors != nullptr, "null argument.");
-    if (!serve_check(sv, c)) return;
-    std::lock_guard<std::mutex> one_call(sv->call_mutex);  // (the call scratch is the handle's)
-    const int64_t ni = sv->n_items;
-    const int32_t k = sv->k, KP = sv->KP;
-    IRS_HIP(hipSetDevice(sv->device));
-    hipStream_t s = nullptr;
-    PhaseClock clock(s);
-    // the user rows, zero-padded to KP on the way up: what the MFMA tiles read
-    sv->user.alloc(static_cast<size_t>(rows) * KP);
-    if (KP != k) IRS_HIP(hipMemsetAsync(sv->user.ptr, 0, static_cast<size_t>(rows) * KP * sizeof(float), s));
-    IRS_HIP(hipMemcpy2DAsync(sv->user.ptr, sizeof(float) * KP, user_factors, sizeof(float) * k, sizeof(float) * k,
-                             static_cast<size_t>(rows), hipMemcpyHostToDevice, s));
-    serve_run<float>(sv, c, s, clock, [&](int64_t b, int64_t m, float *block) {
-      if (irs_gk_scores_device_(sv->user.ptr + b * KP, sv->item.ptr, KP, m, ni, block, s) != IRS_OK)
-        throw std::runtime_error(irs_last_error());
-    });
-  });
-}
-
-}  // extern "C"
+#include "serve_calls.hpp"

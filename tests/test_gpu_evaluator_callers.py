@@ -485,3 +485,88 @@ def test_similarity_path_argument_errors():
     # identity W: the scores are the profile itself; unmasked, every user's own items lead the list
     m = core.get_metrics_similarity(X, W, 0, 200, None, 0, [3], 0)[0]
     assert m.total_user == 200
+
+
+# ------------------------------------------------------- what each call does with the mask rows it is handed
+def _same_metrics(got, want, what):
+    assert len(got) == len(want) and len(got) > 0
+    for a, b in zip(got, want):
+        np.testing.assert_array_equal(a.item_cnt, b.item_cnt, err_msg=what)
+        assert (a.valid_user, a.total_user, a.hit, a.recall, a.ndcg, a.precision, a.map) == \
+            (b.valid_user, b.total_user, b.hit, b.recall, b.ndcg, b.precision, b.map), what
+
+
+def test_mask_columns_outside_the_catalogue_per_call():
+    """A mask row that holds a column ``>= n_items`` or ``< 0`` (``MaskRows`` refuses them, a C-ABI caller may
+    still hand them over: the arrays are edited after the check).  ``get_metrics_masked`` and the sparse
+    similarity call skip such entries - the result is that of the mask without them -, the dense-similarity and
+    factor calls refuse the mask."""
+    U, I, k = 6, 70, 8
+    rns = np.random.RandomState(21)
+    gt = sps.csr_matrix((rns.rand(U, I) > 0.8).astype(np.float64))
+    M = sps.csr_matrix((rns.rand(U, I) > 0.7).astype(np.float64))
+    M.sort_indices()
+    clean, stray = MaskRows(M, I), MaskRows(M, I)
+    rows, ptr_ = [], [0]
+    for r in range(U):  # a stray column at the front, in the middle and at the end of a row, of either sign
+        own = list(M.indices[M.indptr[r]:M.indptr[r + 1]])
+        half = len(own) // 2
+        rows += [[I] + own[:half] + [-1] + own[half:] + [I + 5, -(2 ** 31)],
+                 own[:half] + [2 ** 31 - 1] + own[half:], own + [-3]][r % 3]
+        ptr_.append(len(rows))
+    stray.indptr, stray.indices = np.asarray(ptr_, dtype=np.int64), np.asarray(rows, dtype=np.int32)
+    assert stray.indices.size > clean.indices.size and stray.indices.max() >= I and stray.indices.min() < 0
+    core = EvaluatorCore(gt, [])
+    cutoffs = [1, 5, 20]
+    for dtype in ("float32", "float64"):
+        scores = rns.randn(U, I).astype(dtype)
+        _same_metrics(core.get_metrics_masked(scores, stray, 0, cutoffs, 0, 1),
+                      core.get_metrics_masked(scores, clean, 0, cutoffs, 0, 1), f"masked {dtype}")
+        _same_metrics(core.get_metrics_masked(scores[2:5], stray, 2, cutoffs, 2, 1),
+                      core.get_metrics_masked(scores[2:5], clean, 2, cutoffs, 2, 1), f"masked {dtype}, rows 2 .. 5")
+    X = sps.csr_matrix((rns.rand(U, I) > 0.8) * rns.uniform(0.5, 3.0, (U, I)))
+    W = sps.random(I, I, density=0.2, format="csr", random_state=rns, dtype=np.float64)
+    W.sort_indices()
+    _same_metrics(core.get_metrics_similarity(X, W, 0, U, stray, 0, cutoffs, 0),
+                  core.get_metrics_similarity(X, W, 0, U, clean, 0, cutoffs, 0), "similarity")
+    _same_metrics(core.get_metrics_similarity(X, W, 1, U, stray, 1, cutoffs, 1),
+                  core.get_metrics_similarity(X, W, 1, U, clean, 1, cutoffs, 1), "similarity, rows 1 .. 6")
+    Wd = rns.randn(I, I).astype(np.float32)
+    A, B = rns.randn(U, k).astype(np.float32), rns.randn(I, k).astype(np.float32)
+    assert core.get_metrics_dense_similarity(X, Wd, 0, U, clean, 0, cutoffs, 0)[0].total_user == U
+    assert core.get_metrics_factors(A, B, 0, U, clean, 0, cutoffs, 0)[0].total_user == U
+    with pytest.raises(ValueError, match=r"mask column index out of range\."):
+        core.get_metrics_dense_similarity(X, Wd, 0, U, stray, 0, cutoffs, 0)
+    with pytest.raises(ValueError, match=r"mask column index out of range\."):
+        core.get_metrics_factors(A, B, 0, U, stray, 0, cutoffs, 0)
+
+
+def test_similarity_call_masked_with_the_profile_arrays_themselves(monkeypatch):
+    """The usual caller masks with the rows it scores from and hands the SAME arrays over twice; the library
+    then uploads them once.  Against a copy of the arrays (uploaded on their own): metrics and item counts
+    identical.  Two tiles of columns (the second ragged), three blocks of users (the last ragged), an empty
+    profile, and one profile longer than the rest (the launch order inside its block is not the identity)."""
+    U, I = 100, 2100
+    rns = np.random.RandomState(31)
+    D = (rns.rand(U, I) < 0.01).astype(np.float64)
+    D[11] = 0.0
+    D[50, rns.choice(I, 400, replace=False)] = 1.0
+    X = sps.csr_matrix(D)
+    X.sort_indices()
+    assert X.indices.dtype == np.int32 and X[11].nnz == 0 and X[50].nnz > 2 * np.delete(np.diff(X.indptr), 50).max()
+    W = sps.random(I, I, density=0.01, format="csr", random_state=rns, dtype=np.float64)
+    W.sort_indices()
+    gt = sps.csr_matrix((rns.rand(U, I) > 0.99).astype(np.float64))
+    core = EvaluatorCore(gt, [])
+    same, copied = MaskRows(X, I), MaskRows(X.copy(), I)
+    assert np.shares_memory(same.indices, X.indices) and not np.shares_memory(copied.indices, X.indices)
+    monkeypatch.setenv("IRSPACK_AMD_EVAL_SIM_BLOCK_ROWS", "37")
+    cutoffs = [1, 5, 20]
+    for begin in (0, 3):
+        got = core.get_metrics_similarity(X, W, begin, U, same, begin, cutoffs, begin)
+        want = core.get_metrics_similarity(X, W, begin, U, copied, begin, cutoffs, begin)
+        _same_metrics(got, want, f"users {begin} .. {U}")
+        assert got[0].total_user == U - begin and got[0].valid_user > 0
+    # and the mask did mask: without it, the users' own items lead their lists
+    bare = core.get_metrics_similarity(X, W, 0, U, None, 0, cutoffs, 0)
+    assert not np.array_equal(bare[2].item_cnt, got[2].item_cnt)

@@ -526,3 +526,40 @@ def test_two_calls_give_identical_arrays(servers, factor_servers):
         b = dev.recommend_known_arrays(USERS, 65)
         for x, y in zip(a, b):
             assert x.tobytes() == y.tobytes()
+
+
+# ---- row pointers that do not start at 0 -------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", ["item_knn", "ease"])
+def test_rows_and_exclusions_of_a_larger_matrix_without_rebasing(X, servers, name, monkeypatch):
+    """``recommend_profiles`` through the C ABI with ``x_indptr[0] > 0`` and ``excl_indptr[0] > 0``: 40 rows out of
+    the middle of a larger CSR, their pointers as they stand (the profile entries are read at those offsets, the
+    exclusion entries from the first one of the call) - the same three arrays as with the pointers rebased to 0."""
+    monkeypatch.setenv("IRSPACK_AMD_SERVE_BLOCK", "256")  # (read per call)
+    lib, ptr = _lib.lib(), _lib.ptr
+    h = servers[name]._h
+    rows, first, cutoff = 40, 100, 7
+    xp = np.ascontiguousarray(X.indptr[first:first + rows + 1], dtype=np.int64)
+    xi, xd = np.ascontiguousarray(X.indices, dtype=np.int32), np.ascontiguousarray(X.data, dtype=np.float64)
+    E = sps.csr_matrix((np.random.default_rng(5).random(X.shape) < 0.1).astype(np.float64))
+    ep = np.ascontiguousarray(E.indptr[first + 20:first + 20 + rows + 1], dtype=np.int64)
+    ei = np.ascontiguousarray(E.indices[ep[0]:ep[-1]], dtype=np.int32)
+    assert xp[0] > 0 and ep[0] > 0 and xp[-1] > xp[0] and ep[-1] > ep[0]
+    no_list = np.zeros(1, dtype=np.int64)
+
+    def call(xp_, xi_, xd_, ep_):
+        idx, sc = np.full((rows, cutoff), -7, dtype=np.int32), np.full((rows, cutoff), -7, dtype=np.float32)
+        ln = np.full(rows, -7, dtype=np.int32)
+        _lib.check(lib.irs_serve_recommend_profiles(
+            h, C.c_int64(rows), ptr(xp_, C.c_int64), ptr(xi_, C.c_int32), ptr(xd_, C.c_double), ptr(ep_, C.c_int64),
+            ptr(ei, C.c_int32), C.c_int64(0), ptr(no_list, C.c_int64), ptr(no_list, C.c_int64), C.c_int64(cutoff),
+            ptr(idx, C.c_int32), ptr(sc, C.c_float), ptr(ln, C.c_int32)))
+        return idx, sc, ln
+
+    got = call(xp, xi, xd, ep)
+    want = call(xp - xp[0], np.ascontiguousarray(xi[xp[0]:]), np.ascontiguousarray(xd[xp[0]:]), ep - ep[0])
+    for a, b in zip(got, want):
+        assert a.tobytes() == b.tobytes()
+    assert (got[2] == cutoff).all() and (got[0] >= 0).all()
+    excluded = E[first + 20:first + 20 + rows].toarray() != 0
+    assert not excluded[np.arange(rows)[:, None], got[0]].any()

@@ -86,3 +86,21 @@ def test_mt19937_jump_ahead_arithmetic(tmp_path, portable):
     assert "mt_jump_check ok" in r.stdout
     if portable:
         assert "portable product" in r.stdout
+
+
+_HOST_CXX = shutil.which("g++") or shutil.which("clang++")
+
+
+@pytest.mark.skipif(_HOST_CXX is None, reason="needs a host C++ compiler")
+def test_evaluator_host_preparation_under_address_and_ub_sanitizers(tmp_path):
+    """irspack_amd/csrc/eval_host_prep.hpp - profile, mask and candidate rows, the launch order, the rows per
+    score block (against the five formulas of the entry points, written out), the scan of a sparse W - in a
+    program of its own (tests/host/eval_host_prep_main.cpp), every report fatal."""
+    exe = str(tmp_path / "eval_host_prep_main")
+    src = os.path.join(ROOT, "tests", "host", "eval_host_prep_main.cpp")
+    subprocess.check_call([_HOST_CXX, "-std=c++17", "-O1", "-g", "-pthread", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", src, "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+    assert "eval_host_prep ok" in r.stdout
