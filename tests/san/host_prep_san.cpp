@@ -1,6 +1,7 @@
 // Sanitizer harness of the multi-threaded HOST preparation of libirspack_amd.so (no GPU): the
 // validated CSR copy, the counting-sort transposes and the parallel libstdc++ random stream of
-// irspack_amd/csrc/host_prep.hpp, and the kNN target pass helpers of knn_host_prep.hpp.  Built
+// irspack_amd/csrc/host_prep.hpp, and the kNN construction helpers of knn_host_prep.hpp (the target
+// pass and the rest of a compute call's host logic: tests/host/knn_host_prep_main.cpp).  Built
 // and run by tests/test_host_sanitizers.py with -fsanitize=thread and -fsanitize=address,undefined.
 // Every multi-threaded result is compared with a sequential evaluation.
 #include <cmath>

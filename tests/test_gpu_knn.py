@@ -835,3 +835,79 @@ def test_separable_weighting_tie_order_known_answer():
         sl = slice(got.indptr[i], got.indptr[i + 1])
         np.testing.assert_array_equal(got.indices[sl], sel)
         np.testing.assert_array_equal(got.data[sl], vals[np.searchsorted(cols, sel)])
+
+
+# ---------------------------------------------------------------- buffers kept between calls and computers
+def _binary_items_by_users(n_users, n_items, per_item, seed):
+    """items x users, binary, about `per_item` stored entries per item"""
+    rng2 = np.random.default_rng(seed)
+    nnz = n_items * per_item
+    X = sps.csr_matrix((np.ones(nnz), (rng2.integers(0, n_items, nnz), rng2.integers(0, n_users, nnz))),
+                       shape=(n_items, n_users))
+    X.data[:] = 1.0
+    X.sort_indices()
+    return X
+
+
+def test_buffers_are_handed_over_between_computers():
+    """A destroyed computer leaves its streams, its arena and its page-locked stage to the next one on the
+    device: a small computer (two calls - the second one stages its result), a 17,000-item one (the arena
+    left behind is too small for it), a small one again (it takes over a larger arena than it needs).
+    Every result is the oracle's."""
+    small = _binary_items_by_users(300, 200, 15, 41)
+    large = _binary_items_by_users(300, 17000, 5, 42)
+    a, oa = make("cosine", small, shrinkage=0.0, normalize=True)
+    want_small = oa.compute_similarity(small, 20)
+    first = a.compute_similarity(small, 20)
+    second = a.compute_similarity(small, 20)  # (not the computer's first call: through the stage)
+    assert_same_csr(first, want_small)
+    assert_same_csr(second, want_small)
+    for x, y in ((first.indptr, second.indptr), (first.indices, second.indices), (first.data, second.data)):
+        np.testing.assert_array_equal(x, y)
+    a.__del__()
+    b, ob = make("cosine", large, shrinkage=0.0, normalize=True)
+    assert_same_csr(b.compute_similarity(large, 20), ob.compute_similarity(large, 20))
+    b.__del__()
+    c, _ = make("cosine", small, shrinkage=0.0, normalize=True)
+    assert_same_csr(c.compute_similarity(small, 20), want_small)
+
+
+def test_fetch_csc_after_a_staged_call_then_fetch():
+    """irs_knn_fetch_csc borrows the page-locked stage of a staged call; irs_knn_fetch afterwards still gives
+    the CSR result (from the device)."""
+    import ctypes as C
+
+    from irspack_amd._lib import check, lib, ptr
+
+    for M in (_binary_items_by_users(300, 200, 15, 43), _binary_items_by_users(300, 17000, 5, 44)):
+        g, _ = make("cosine", M, shrinkage=0.0, normalize=True)
+        g.compute_similarity(M, 20)
+        csr = g.compute_similarity(M, 20)  # (the second call stages its result)
+        want = remove_diagonal(csr.copy()).tocsc()
+        want.sort_indices()
+        N, nnz = M.shape[0], csr.nnz
+        cp, ri, cv = np.empty(N + 1, np.int64), np.empty(nnz, np.int32), np.empty(nnz, np.float64)
+        check(lib().irs_knn_fetch_csc(g._h, C.c_int64(0), ptr(cp, C.c_int64), ptr(ri, C.c_int32), ptr(cv, C.c_double)))
+        np.testing.assert_array_equal(cp, want.indptr)
+        np.testing.assert_array_equal(ri, want.indices)
+        np.testing.assert_array_equal(cv, want.data)
+        rp, ci, rv = np.empty(N + 1, np.int64), np.empty(nnz, np.int32), np.empty(nnz, np.float64)
+        check(lib().irs_knn_fetch(g._h, ptr(rp, C.c_int64), ptr(ci, C.c_int32), ptr(rv, C.c_double)))
+        np.testing.assert_array_equal(rp, csr.indptr)
+        np.testing.assert_array_equal(ci, csr.indices)
+        np.testing.assert_array_equal(rv, csr.data)
+
+
+@pytest.mark.parametrize("chunks", ["1", "3"])
+def test_last_stats_count_the_multiply_adds_of_the_call(chunks, monkeypatch):
+    """irs_knn_last_stats: `macs` is the sum, over the call's target entries, of the length of the feature row
+    the entry selects; `kernel_ms` spans the call's launches."""
+    monkeypatch.setenv("IRSPACK_AMD_KNN_CHUNKS", chunks)
+    for M in (_binary_items_by_users(300, 200, 15, 45), _binary_items_by_users(300, 17000, 5, 46)):
+        g, _ = make("cosine", M, shrinkage=0.0, normalize=True)
+        row_len = np.bincount(M.indices, minlength=M.shape[1]).astype(np.int64)  # feature u: entries of column u
+        for sel in (None, (M.shape[0] // 3, M.shape[0] - 7)):
+            g.compute_similarity(M, 10, rows=sel)
+            lo, hi = (0, M.shape[0]) if sel is None else sel
+            assert g.last_macs == int(row_len[M.indices[M.indptr[lo]:M.indptr[hi]]].sum())
+            assert g.last_kernel_ms > 0

@@ -1,10 +1,15 @@
-"""The multi-threaded HOST preparation of the library (counting-sort transposes, validated CSR
-copies, the parallel libstdc++ random stream, the kNN per-row pass - irspack_amd/csrc/
-host_prep.hpp, knn_host_prep.hpp) compiled on its own with g++ and run under ThreadSanitizer and
-AddressSanitizer + UBSan ("race detection").  GPU sanitizers are not
-available on the pool; this covers the code that runs on host threads.  The harness
-(tests/san/host_prep_san.cpp) also compares every multi-threaded result with a sequential one,
-and the parallel random stream with std::normal_distribution<float> itself (> 2^18 values)."""
+"""The multi-threaded HOST preparation of the library compiled on its own with the host compiler and run under
+ThreadSanitizer and AddressSanitizer + UBSan ("race detection").  GPU sanitizers are not
+available on the pool; this covers the code that runs on host threads:
+- tests/san/host_prep_san.cpp: irspack_amd/csrc/host_prep.hpp (counting-sort transposes, validated CSR copies, the
+  parallel libstdc++ random stream) and the construction helpers of knn_host_prep.hpp (host_csr, transpose,
+  transpose_pattern, column_counts, the weight tables, for_rows_parallel).  It compares every multi-threaded
+  result with a sequential one, and the parallel random stream with std::normal_distribution<float> itself
+  (> 2^18 values).
+- tests/host/knn_host_prep_main.cpp: the rest of knn_host_prep.hpp, i.e. what a kNN compute call does on the host
+  before it launches - entry scan, chunk cuts, the threaded target pass, launch order, variant choice, arena layout.
+- tests/host/eval_host_prep_main.cpp: eval_host_prep.hpp.
+The stream, event and buffer handling of knn.hip itself needs a device and is not compiled here."""
 import os
 import shutil
 import subprocess
@@ -104,3 +109,35 @@ def test_evaluator_host_preparation_under_address_and_ub_sanitizers(tmp_path):
     assert r.returncode == 0, r.stderr[-4000:]
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
     assert "eval_host_prep ok" in r.stdout
+
+
+def _knn_host_prep(tmp_path, flags, env_extra):
+    exe = str(tmp_path / "knn_host_prep_main")
+    src = os.path.join(ROOT, "tests", "host", "knn_host_prep_main.cpp")
+    subprocess.check_call([_HOST_CXX, "-std=c++17", "-O1", "-g", "-pthread", "-ffp-contract=off", *flags,
+                           "-fno-omit-frame-pointer", src, "-o", exe])
+    return subprocess.run([exe], env=dict(os.environ, **env_extra), capture_output=True, text=True, timeout=600)
+
+
+@pytest.mark.skipif(_HOST_CXX is None, reason="needs a host C++ compiler")
+def test_knn_host_preparation_under_address_and_ub_sanitizers(tmp_path):
+    """irspack_amd/csrc/knn_host_prep.hpp - the entry scan, the chunk cuts, the threaded target pass (malformed row
+    pointers and indices included: nothing outside the arrays is read), the launch order, the kernel-variant choice
+    (against the former chain of conditions, written out), the arena layout - in a program of its own
+    (tests/host/knn_host_prep_main.cpp), every report fatal."""
+    r = _knn_host_prep(tmp_path, ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], {})
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+    assert "knn_host_prep ok" in r.stdout
+
+
+@pytest.mark.skipif(_HOST_CXX is None, reason="needs a host C++ compiler")
+def test_knn_host_preparation_under_thread_sanitizer(tmp_path):
+    """The same program under ThreadSanitizer: the target pass on 1, 2 and 5 threads fills its three tables and
+    sets its flags without a race."""
+    r = _knn_host_prep(tmp_path, ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1 second_deadlock_stack=1"})
+    if "unexpected memory mapping" in r.stderr or "personality" in r.stderr:
+        pytest.skip("ThreadSanitizer cannot map its shadow memory in this container: " + r.stderr[:200])
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert "WARNING: ThreadSanitizer" not in r.stderr, r.stderr[-4000:]
+    assert "knn_host_prep ok" in r.stdout
