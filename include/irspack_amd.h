@@ -635,6 +635,72 @@ irs_status irs_nmf_fit(int64_t n_users, int64_t n_items, const int64_t *indptr, 
                        float l2_H, double tol, int64_t max_iter, int32_t update_H, int32_t device, int64_t *n_iter,
                        double *violations /* may be NULL */, irs_nmf_stats_t *stats /* may be NULL */);
 
+/* ------------------------------------------------------------------ BPR
+ * BPRFMRecommender (src/irspack/recommenders/bpr.py wraps LightFM; the arithmetic here is this library's own
+ * synchronous mini-batch form of LightFM's per-sample step - BPR loss, Adagrad, item biases, no user bias -
+ * DESIGN.md section 14).  State, all float32: U [n_users, k], V [n_items, k], item bias b [n_items], the Adagrad
+ * accumulators GU, GV, Gb of the same shapes (1 at the start) and an epoch counter.  Without initial tables U and V
+ * are uniform in (-0.5, 0.5) / k from `seed` through the library's counter-based generator, b = 0.
+ * Positives: the stored entries of X (CSR float32) with value > 0; the values are not used otherwise.
+ *   epoch    every positive of a user with an unseen item once, in an order that depends on (seed, epoch) alone
+ *            (a keyed Feistel permutation of the positions); the negative of a position is uniform over the items
+ *            its user has no positive on - the r-th unseen item by a binary search in the user's row, r from the
+ *            generator at (seed, epoch, position), no rejection loop.  A user with a positive on every item has no
+ *            negative: its positives are skipped and counted.
+ *   batch    batch_size consecutive triples (u, i, j) of that order (the last batch of an epoch may be shorter),
+ *            synchronous - every triple reads the parameters as the batch found them:
+ *              x = U[u].(V[i] - V[j]) + b[i] - b[j],  w = 1 / (1 + exp(x))
+ *              gU[u] -= w (V[i] - V[j]);  gV[i] -= w U[u];  gV[j] += w U[u];  gb[i] -= w;  gb[j] += w
+ *            summed over the batch per row; every row the batch touched then gets gU[r] += user_alpha U[r]
+ *            (gV, gb: item_alpha) once, and theta -= learning_rate g / sqrt(G), G += g^2 element by element (G is
+ *            read before it is updated).  Untouched rows keep their bytes.
+ * The per-row sums are 64-bit fixed-point integers (scale 2^s, s from the batch length: irs_bpr_stats) added with
+ * integer atomics, so they do not depend on the order of arrival: two runs give identical bytes.  The scale assumes
+ * |theta| < 2^8 for every parameter; a call after which one is not (or is not finite) returns IRS_RUNTIME_ERROR and
+ * the state is lost.
+ *   create        validates and keeps the arguments; the device is first used by the first other call that needs
+ *                 it, so every argument check of every call comes before any device work.
+ *   run_epochs    n_epochs epochs from the current state and epoch counter: per batch three launches on one
+ *                 stream, no copy and no synchronisation inside an epoch.
+ *   sample        the triples run_epochs uses at positions [first, first + count) of `epoch` (the same kernel), into
+ *                 users / pos / neg; 0 <= first, first + count <= n_positives - n_skipped_positives.
+ *   step_triples  ONE synchronous batch on the caller's n triples through the kernels of an epoch (the epoch
+ *                 counter stays); a triple's rows need not be related by X.
+ *   get_state     any of the six arrays and epoch may be NULL.  set_state replaces all of them.
+ * IRS_INVALID_ARGUMENT before any device work: the matrix checks of irs_truncsvd_create (unsorted or duplicate
+ * indices within a row among them), k < 1 or k > 512, batch_size < 1, a negative or non-finite alpha or
+ * learning_rate, learning_rate == 0, a non-finite entry (or one of magnitude >= 2^8) in the initial tables or in a
+ * state being set, an accumulator <= 0 in a state being set, a triple out of range in step_triples.
+ * IRS_RUNTIME_ERROR: no device, not enough device memory, a diverged fit.  One handle is used by one thread at a
+ * time. */
+typedef struct irs_bpr irs_bpr;
+typedef struct {
+  int64_t n_positives;         /* stored entries > 0 */
+  int64_t n_skipped_full_rows; /* users with a positive on every item ... */
+  int64_t n_skipped_positives; /* ... and their positives, which no epoch uses */
+  int64_t batches_per_epoch;
+  int32_t lanes_per_triple;    /* of the gradient and apply kernels at this k */
+  int32_t scale_log2;          /* s of a full batch */
+  double epoch_ms;             /* HIP events round the last epoch run_epochs ran */
+  double sample_ms;            /* that epoch by phase, collected only with IRSPACK_AMD_BPR_PHASES=1 in the */
+  double grad_ms;              /* environment when the handle is made (two more events per launch), else 0 */
+  double apply_ms;
+} irs_bpr_stats_t;
+irs_status irs_bpr_create(int64_t n_users, int64_t n_items, const int64_t *indptr, const int32_t *indices,
+                          const float *data, int32_t k, float user_alpha, float item_alpha, float learning_rate,
+                          int64_t batch_size, uint64_t seed, const float *user_init /* may be NULL */,
+                          const float *item_init /* may be NULL */, int32_t device, irs_bpr **out);
+irs_status irs_bpr_run_epochs(irs_bpr *t, int64_t n_epochs);
+irs_status irs_bpr_sample(irs_bpr *t, int64_t epoch, int64_t first, int64_t count, int32_t *users, int32_t *pos,
+                          int32_t *neg);
+irs_status irs_bpr_step_triples(irs_bpr *t, int64_t n, const int32_t *users, const int32_t *pos, const int32_t *neg);
+irs_status irs_bpr_get_state(irs_bpr *t, float *U, float *V, float *b, float *GU, float *GV, float *Gb,
+                             int64_t *epoch);
+irs_status irs_bpr_set_state(irs_bpr *t, const float *U, const float *V, const float *b, const float *GU,
+                             const float *GV, const float *Gb, int64_t epoch);
+irs_status irs_bpr_stats(irs_bpr *t, irs_bpr_stats_t *out);
+irs_status irs_bpr_destroy(irs_bpr *t);
+
 /* ------------------------------------------------------------------ serving
  * Batch top-k recommendations from a model that stays on the device (the reference's path:
  * utils/id_mapping.py:172-223, 399-453 - get_score_remove_seen on the host, then

@@ -122,6 +122,21 @@ class NmfStatsStruct(C.Structure):  # irs_nmf_stats_t
     ]
 
 
+class BprStatsStruct(C.Structure):  # irs_bpr_stats_t
+    _fields_ = [
+        ("n_positives", C.c_int64),
+        ("n_skipped_full_rows", C.c_int64),
+        ("n_skipped_positives", C.c_int64),
+        ("batches_per_epoch", C.c_int64),
+        ("lanes_per_triple", C.c_int32),
+        ("scale_log2", C.c_int32),
+        ("epoch_ms", C.c_double),
+        ("sample_ms", C.c_double),
+        ("grad_ms", C.c_double),
+        ("apply_ms", C.c_double),
+    ]
+
+
 ABI_VERSION = 4  # IRS_ABI_VERSION of include/irspack_amd.h
 # IRS_EXCHANGE_* of include/irspack_amd.h: how irs_ials_sharded_step moves the solved rows
 EXCHANGE_MODES = {"auto": 0, "broadcast": 1, "mesh": 2, "peer": 3}
@@ -194,6 +209,14 @@ EXPORTED_SYMBOLS = [
     "irs_truncsvd_stats",
     "irs_truncsvd_destroy",
     "irs_nmf_fit",
+    "irs_bpr_create",
+    "irs_bpr_run_epochs",
+    "irs_bpr_sample",
+    "irs_bpr_step_triples",
+    "irs_bpr_get_state",
+    "irs_bpr_set_state",
+    "irs_bpr_stats",
+    "irs_bpr_destroy",
     "irs_eval_create",
     "irs_eval_destroy",
     "irs_eval_get_metrics",
@@ -242,6 +265,17 @@ ARGTYPES = {
     "irs_nmf_fit": [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int64,
                     C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_float, C.c_double,
                     C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_void_p],
+    "irs_bpr_create": [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                       C.c_int32, C.c_float, C.c_float, C.c_float, C.c_int64, C.c_uint64, C.POINTER(C.c_float),
+                       C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_void_p)],
+    "irs_bpr_run_epochs": [C.c_void_p, C.c_int64],
+    "irs_bpr_sample": [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                       C.POINTER(C.c_int32)],
+    "irs_bpr_step_triples": [C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+    "irs_bpr_get_state": [C.c_void_p] + [C.POINTER(C.c_float)] * 6 + [C.POINTER(C.c_int64)],
+    "irs_bpr_set_state": [C.c_void_p] + [C.POINTER(C.c_float)] * 6 + [C.c_int64],
+    "irs_bpr_stats": [C.c_void_p, C.c_void_p],
+    "irs_bpr_destroy": [C.c_void_p],
     "irs_eval_get_metrics_dense_similarity": [
         C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
         C.POINTER(C.c_double), C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32,

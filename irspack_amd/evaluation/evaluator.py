@@ -299,8 +299,10 @@ class Evaluator:
 
     def _factor_operands(self, model: Any) -> Optional[Any]:
         """``(user factors (U, k), item factors (I, k))`` when the model scores as a float32 product of two
-        factor tables - ``z @ components_`` of the truncated SVD, ``W @ H`` of NMF - through its class's own
-        ``get_score_block``; ``None`` for anything else (other dtypes, more factors than the device call takes)."""
+        factor tables - ``z @ components_`` of the truncated SVD, ``W @ H`` of NMF, ``[U | 1] @ [V | b]^T`` of a
+        trained BPR model - through its class's own ``get_score_block``; ``None`` for anything else (other dtypes,
+        more factors than the device call takes)."""
+        from ..recommenders.bpr import BPRFMRecommender
         from ..recommenders.nmf import NMFRecommender
         from ..recommenders.truncsvd import TruncatedSVDRecommender
 
@@ -315,6 +317,10 @@ class Evaluator:
             if type(model).get_score_block is not NMFRecommender.get_score_block:
                 return None
             users, items = getattr(model, "W", None), getattr(model, "H", None)
+        elif isinstance(model, BPRFMRecommender):
+            if type(model).get_score_block is not BPRFMRecommender.get_score_block or model.trainer is None:
+                return None
+            users, items = model.factor_tables()
         else:
             return None
         for F in (users, items):

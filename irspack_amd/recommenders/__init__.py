@@ -2,6 +2,8 @@
 the recommenders whose compiled core is rebuilt here."""
 
 from .base import BaseRecommender, BaseSimilarityRecommender, BaseUserSimilarityRecommender
+from .base_earlystop import BaseRecommenderWithEarlyStopping
+from .bpr import BPRFMRecommender
 from .dense_slim import DenseSLIMRecommender
 from .edlae import EDLAERecommender
 from .ials import IALSRecommender
@@ -9,6 +11,7 @@ from .knn import (AsymmetricCosineKNNRecommender, CosineKNNRecommender, JaccardK
                   P3alphaRecommender, RP3betaRecommender, TverskyIndexKNNRecommender)
 from .nmf import NMFRecommender
 from .slim import SLIMRecommender
+from .toppop import TopPopRecommender
 from .truncsvd import TruncatedSVDRecommender
 from .user_knn import AsymmetricCosineUserKNNRecommender, CosineUserKNNRecommender
 
@@ -17,4 +20,5 @@ __all__ = ["BaseRecommender", "BaseSimilarityRecommender", "IALSRecommender",
            "TverskyIndexKNNRecommender", "P3alphaRecommender", "RP3betaRecommender",
            "BaseUserSimilarityRecommender", "CosineUserKNNRecommender",
            "AsymmetricCosineUserKNNRecommender", "SLIMRecommender", "DenseSLIMRecommender",
-           "EDLAERecommender", "TruncatedSVDRecommender", "NMFRecommender"]
+           "EDLAERecommender", "TruncatedSVDRecommender", "NMFRecommender",
+           "BaseRecommenderWithEarlyStopping", "BPRFMRecommender", "TopPopRecommender"]

@@ -10,7 +10,6 @@ follows ``base_earlystop.py:106-149`` without the Optuna / progress-bar parts.
 
 import enum
 import pickle
-from io import BytesIO
 from typing import IO, Any, Callable, Optional
 
 import numpy as np
@@ -20,7 +19,7 @@ from .._threading import get_n_threads
 from ._ials_core import IALSModelConfigBuilder, IALSSolverConfigBuilder
 from ._ials_core import IALSTrainer as CoreTrainer
 from ._ials_core import LossType, SolverType
-from .base import BaseRecommender
+from .base_earlystop import BaseRecommenderWithEarlyStopping
 
 
 def _enum_by_name(enum_cls: Any, name: str) -> Any:
@@ -145,7 +144,7 @@ def compute_reg_scale(X: sps.csr_matrix, alpha0: float, nu: float) -> float:
     return float(((nnz_row + alpha0 * I) ** nu).sum()) + float(((nnz_col + alpha0 * U) ** nu).sum())
 
 
-class IALSRecommender(BaseRecommender):
+class IALSRecommender(BaseRecommenderWithEarlyStopping):
     """ials.py:245-562.  Same constructor arguments and defaults; ``device`` is an extra
     keyword.  ``user_features`` / ``item_features`` (dense or CSR, one row per user / item)
     switch on the feature-aware model (trainer hpp:722-789)."""
@@ -161,7 +160,7 @@ class IALSRecommender(BaseRecommender):
                  user_features: Any = None, item_features: Any = None,
                  lambda_user_feature: float = 0.0, lambda_item_feature: float = 0.0,
                  feature_warmup_epochs: int = 0) -> None:
-        super().__init__(X_train_all)
+        super().__init__(X_train_all, train_epochs=train_epochs)
         # ials.py:421-432
         self.user_features = None if user_features is None else _feature_matrix_as_float32(user_features)
         self.item_features = None if item_features is None else _feature_matrix_as_float32(item_features)
@@ -170,7 +169,6 @@ class IALSRecommender(BaseRecommender):
         self.lambda_user_feature = lambda_user_feature
         self.lambda_item_feature = lambda_item_feature
         self.feature_warmup_epochs = feature_warmup_epochs
-        self.train_epochs = train_epochs
         self.n_components = n_components
         self.alpha0 = alpha0
         self.reg = reg
@@ -193,8 +191,6 @@ class IALSRecommender(BaseRecommender):
         self.prediction_time_ialspp_iteration = prediction_time_ialspp_iteration
         self.device = device
         self.trainer: Optional[IALSTrainer] = None
-        self.best_state: Optional[bytes] = None
-        self.learnt_config = {}
 
     @classmethod
     def _scale_X(cls, X: sps.csr_matrix, scheme: IALSConfigScaling, epsilon: float) -> sps.csr_matrix:
@@ -219,50 +215,9 @@ class IALSRecommender(BaseRecommender):
             feature_warmup_epochs=self.feature_warmup_epochs,
         )
 
-    # -- base_earlystop.py:80-149 ------------------------------------------
-    def start_learning(self) -> None:
-        self.trainer = self._create_trainer()
-
-    def run_epoch(self) -> None:
-        self.trainer_as_ials.run_epoch()
-
-    def save_state(self) -> None:
-        with BytesIO() as ofs:
-            self.trainer_as_ials.save_state(ofs)
-            self.best_state = ofs.getvalue()
-
-    def load_state(self) -> None:
-        if self.best_state is None:
-            raise RuntimeError("'load_state' called before achieving any results.")
-        with BytesIO(self.best_state) as ifs:
-            self.trainer_as_ials.load_state(ifs)
-
-    def _learn(self) -> None:
-        self.learn_with_evaluator(None, max_epoch=self.train_epochs)
-
-    def learn_with_evaluator(self, evaluator: Any, max_epoch: int = 128, validate_epoch: int = 5,
-                             score_degradation_max: int = 5) -> None:
-        """base_earlystop.py:106-149 without the progress bar / Optuna hooks: every
-        ``validate_epoch`` epochs the evaluator scores the model; the best state is kept and
-        restored at the end, and ``score_degradation_max`` validations in a row without a new best
-        end the fit.  ``evaluator=None``: exactly ``max_epoch`` epochs."""
-        self.start_learning()
-        best, misses = -float("inf"), 0
-        for done in range(1, max_epoch + 1):
-            self.run_epoch()
-            if evaluator is None or done % validate_epoch:
-                continue
-            score = evaluator.get_target_score(self)
-            if score > best:
-                best, misses = score, 0
-                self.save_state()
-                self.learnt_config["train_epochs"] = done
-                continue
-            misses += 1
-            if misses >= score_degradation_max:
-                break
-        if evaluator is not None and self.best_state is not None:
-            self.load_state()
+    # the epoch loop, early stopping and the best state: BaseRecommenderWithEarlyStopping
+    def _trainer_or_raise(self, caller: str) -> IALSTrainer:
+        return self.trainer_as_ials
 
     @property
     def trainer_as_ials(self) -> IALSTrainer:

@@ -8,7 +8,8 @@ the score block never leaves the device, three small arrays come home per call.
 
 The model kinds are the ones the ``Evaluator`` scores on the device: sparse similarity weights (item-kNN, P3alpha,
 RP3beta, SLIM: ``X_train[u] @ W``; user-kNN: ``U[u] @ X_train``) and dense ones (EASE, EDLAE) - the host product
-bit for bit, float64 - and factor models (iALS, truncated SVD, NMF) - float32 through the MFMA tiles.  A model whose
+bit for bit, float64 - and factor models (iALS, truncated SVD, NMF, BPR with its item bias as one more factor) -
+float32 through the MFMA tiles.  A model whose
 class overrides ``get_score_block`` scores some other way and is not recognised (``TypeError``).
 
 The operands are copied when the ``DeviceRecommender`` is made: a model that is trained further needs a new one
@@ -24,6 +25,7 @@ import scipy.sparse as sps
 
 from . import _lib
 from ._lib import check, lib, ptr
+from .recommenders.base import BaseRecommender
 
 _SCORE_DTYPES = (np.float32, np.float64)
 MAX_FACTORS = 576  # of irs_serve_create_factors
@@ -39,6 +41,7 @@ def model_operands(model: Any) -> Optional[Tuple[str, Tuple[Any, ...]]]:
     The rules are the Evaluator's (``_similarity_weights``, ``_dense_similarity_weights``, ``_factor_operands``, a
     trained iALS recommender): the class's own ``get_score_block`` must not be overridden."""
     from .recommenders.base import BaseSimilarityRecommender, BaseUserSimilarityRecommender
+    from .recommenders.bpr import BPRFMRecommender
     from .recommenders.ials import IALSRecommender
     from .recommenders.nmf import NMFRecommender
     from .recommenders.truncsvd import TruncatedSVDRecommender
@@ -64,8 +67,14 @@ def model_operands(model: Any) -> Optional[Tuple[str, Tuple[Any, ...]]]:
                 X.dtype != np.float64 or U.shape != (model.n_users, model.n_users):
             return None
         return "user_similarity", (U, X)
-    if isinstance(model, (TruncatedSVDRecommender, NMFRecommender)):
-        if isinstance(model, TruncatedSVDRecommender):
+    if isinstance(model, (TruncatedSVDRecommender, NMFRecommender, BPRFMRecommender)):
+        if isinstance(model, BPRFMRecommender):
+            # [U | 1] and [V | b]^T: K + 1 columns, held by the model per trained state (a model that is trained
+            # further hands out new tables, so both count as new operands)
+            if own is not BPRFMRecommender.get_score_block or model.trainer is None:
+                return None
+            users, items = model.factor_tables()
+        elif isinstance(model, TruncatedSVDRecommender):
             if own is not TruncatedSVDRecommender.get_score_block:
                 return None
             users = getattr(model, "z_", None)
@@ -207,7 +216,7 @@ class DeviceRecommender:
         found = model_operands(model)
         if found is None:
             raise TypeError(f"{type(model).__name__} is not a model the device can serve: sparse or dense "
-                            "similarity weights, truncated SVD, NMF or a trained iALS recommender, scoring through "
+                            "similarity weights, truncated SVD, NMF or a trained iALS or BPR recommender, scoring through "
                             "its class's own get_score_block.")
         self.kind, operands = found
         self._model = weakref.ref(model) if weak_model else (lambda: model)
@@ -217,6 +226,9 @@ class DeviceRecommender:
         self._h = C.c_void_p()
         self._users: Optional[np.ndarray] = None
         self._profiles: Optional[sps.csr_matrix] = None
+        # (models without get_score_cold_user, as in the reference: user-kNN and BPR)
+        self._cold_users = self.kind != "user_similarity" and \
+            getattr(type(model), "get_score_cold_user", None) is not BaseRecommender.get_score_cold_user
         dev = C.c_int32(self.device)
         if self.kind in ("similarity", "user_similarity"):
             profiles, W = operands
@@ -371,7 +383,7 @@ class DeviceRecommender:
                                   per_user_allowed: Optional[Sequence[Sequence[int]]] = None,
                                   forbidden: Optional[Sequence[Sequence[int]]] = None) -> ArrayTriple:
         cutoff = self._check_cutoff(cutoff)
-        if self.kind == "user_similarity":
+        if not self._cold_users:
             raise NotImplementedError(f"get_score_cold_user is not implemented for {self._model_name}!")
         Xc = _as_profile_rows(X, self.n_items)
         lists = self._lists(Xc.shape[0], allowed, per_user_allowed)
