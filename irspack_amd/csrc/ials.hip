@@ -18,6 +18,7 @@
 #include "common.hpp"
 #include "comm.hpp"
 #include "host_prep.hpp"
+#include "ials_host_plan.hpp"
 
 #include <hip/hip_ext.h>
 #include "ials_kernels.hpp"
@@ -53,13 +54,6 @@ void require_device(int device) {
 
 namespace ials {
 
-static int padded_k(int64_t K) {
-  if (K <= 16) return 16;
-  if (K <= 32) return 32;
-  if (K <= 64) return 64;
-  return static_cast<int>(ceil_div(K, 64) * 64);
-}
-
 static int chunk_size() {
   static int v = [] {
     const char *e = std::getenv("IRSPACK_AMD_IALS_CHUNK");
@@ -70,32 +64,20 @@ static int chunk_size() {
   return v;
 }
 
-static int max_chunks() { return 256; }
-
 // One CSR orientation resident on the device, with its longest-first task list.
-struct Side {
+// (PlanCounts, ials_host_plan.hpp: n_tasks, n_short, mf_class, reg_min ... - what plan_tasks counted)
+struct Side : PlanCounts {
   int64_t n_rows = 0, n_other = 0, row_begin = 0, row_end = 0, nnz = 0;
   DeviceBuffer<int32_t> indptr, indices;
   DeviceBuffer<float> data, reg;
   DeviceBuffer<Task> tasks;
   DeviceBuffer<SplitRow> split;
   DeviceBuffer<FoldGroup> fold;  // groups of partial Gramians summed before the split rows are finished
-  int32_t n_fold = 0;
   DeviceBuffer<int32_t> rows_by_len;  // rows [row_begin, row_end) longest first (iALS++ launch order)
-  int32_t n_tasks = 0, n_split = 0, n_slots = 0, n_long = 0;
-  // tasks at the end of the (longest-first) list with <= SHORT_MAX (n_short) / <= 16 entries
-  int32_t n_short = 0, n_short16 = 0, n_short8 = 0;
-  int64_t long_entries = 0;  // stored entries of the tasks [0, n_tasks - n_short)
-  // matrix-free CG at 128 < K <= 256 (ials_mf_kernels.hpp): rows_by_len is cut into the
-  // level-synchronous rows (more than MF_NCAP entries, chunked) and the resident classes of
-  // MF_CAPS; mf_class[c] = first index of class c in rows_by_len, [MF_CLASSES] = end
-  DeviceBuffer<MfLongRow> mf_lrows;
+  DeviceBuffer<MfLongRow> mf_lrows;   // matrix-free CG at 128 < K <= 256 (ials_mf_kernels.hpp)
   DeviceBuffer<MfChunk> mf_chunks;
-  int32_t mf_n_lrows = 0, mf_n_chunks = 0, mf_class[MF_CLASSES + 1] = {};
   bool unit = false;  // every stored confidence is exactly 1 (UNIT kernels)
   bool positive = false;  // every stored confidence is > 0 (eigenbasis short-row kernels)
-  float reg_min = 0.f;    // smallest per-row regulariser of the rows [row_begin, row_end)
-  bool has_empty = false; // some row stores no entry (feature-aware step, hpp:639-653)
   bool entries_ready = false, indptr_ready = false;  // the device arrays were filled ahead of build()
 
   // The gather pipeline loads whole 64-entry blocks up to two blocks past a row's end: 320 zero entries
@@ -121,10 +103,15 @@ struct Side {
     }
     IRS_HIP(hipStreamSynchronize(s));
   }
-  void upload_indptr(const HostCsr &m, hipStream_t s) {
+  static std::vector<int32_t> indptr32(const HostCsr &m) {
     std::vector<int32_t> ip32(m.rows + 1);
-    for (int64_t r = 0; r <= m.rows; r++) ip32[r] = static_cast<int32_t>(m.indptr[r]);
-    indptr.upload(ip32, s);
+    parallel_ranges(m.rows + 1, [&](int64_t r0, int64_t r1) {
+      for (int64_t r = r0; r < r1; r++) ip32[r] = static_cast<int32_t>(m.indptr[r]);
+    });
+    return ip32;
+  }
+  void upload_indptr(const HostCsr &m, hipStream_t s) {
+    indptr.upload(indptr32(m), s);
     IRS_HIP(hipStreamSynchronize(s));
     indptr_ready = true;
   }
@@ -148,143 +135,60 @@ struct Side {
       unit = std::all_of(m.data.begin(), m.data.end(), [](float v) { return v == 1.0f; });
       positive = unit || std::all_of(m.data.begin(), m.data.end(), [](float v) { return v > 0.0f; });
     }
-    std::vector<int32_t> ip32(m.rows + 1);
-    std::vector<float> regs(m.rows);
-    ip32[m.rows] = static_cast<int32_t>(m.indptr[m.rows]);
-    parallel_ranges(m.rows, [&](int64_t r0, int64_t r1) {  // (10 M powf at the 10 M x 1 M shape)
-      for (int64_t r = r0; r < r1; r++) {
-        ip32[r] = static_cast<int32_t>(m.indptr[r]);
-        // Solver::compute_reg, hpp:117-120, evaluated in float like the reference
-        const int64_t nz = m.indptr[r + 1] - m.indptr[r];
-        regs[r] = cfg.reg * std::pow(cfg.alpha0 * m.cols + nz, cfg.nu);
-      }
-    });
-    reg_min = 0.f;
-    for (int64_t r = rb; r < re; r++) reg_min = r == rb ? regs[r] : std::min(reg_min, regs[r]);
-    has_empty = false;
-    for (int64_t r = 0; r < m.rows && !has_empty; r++) has_empty = m.indptr[r + 1] == m.indptr[r];
+    const std::vector<int32_t> ip32 = indptr32(m);
     const int CH = chunk_size();
     // (read per build, not once per process: the tests lower it to fold rows of 10^4 entries)
     const char *long_env = std::getenv("IRSPACK_AMD_IALS_CHUNK_LONG");
     const int32_t chunk_long = std::max(CH, long_env ? std::atoi(long_env) : 16384);
-    std::vector<Task> tk;
-    std::vector<SplitRow> sp;
-    std::vector<FoldGroup> fg;
-    tk.reserve(re - rb);
-    int32_t slots = 0;
-    for (int64_t r = rb; r < re; r++) {
-      const int32_t b = ip32[r], e = ip32[r + 1], nz = e - b;
-      if (nz > CH) {
-        // a bounded number of chunks per row: the second kernel adds a row's partials one after
-        // the other, and a chunk is one wave's serial work (the longest chunk is the floor of
-        // the half-step: 4.4 M entries in 32 chunks were 16 ms of one wave at K = 128)
-        // (up to 32 chunks of any length, more only to keep a chunk below 16 K entries: the
-        // ML-20M shape's longest row - 116 k entries - stays at 32 chunks and needs no fold pass)
-        const int32_t nch = std::min<int32_t>(
-            (nz + CH - 1) / CH, std::max<int32_t>(32, std::min<int32_t>(max_chunks(), (nz + chunk_long - 1) / chunk_long)));
-        const int32_t per = (((nz + nch - 1) / nch) + 3) & ~3;
-        SplitRow sr{static_cast<int32_t>(r), slots, 0, nz, 1};
-        for (int32_t c = b; c < e; c += per) {
-          tk.push_back(Task{static_cast<int32_t>(r), c, std::min(c + per, e), slots++});
-          sr.n_slots++;
-        }
-        if (sr.n_slots > FOLD_MIN) {
-          for (int32_t g = 0; g < sr.n_slots; g += FOLD_GROUP)
-            fg.push_back(FoldGroup{sr.first_slot + g, std::min(FOLD_GROUP, sr.n_slots - g)});
-          sr.n_slots = (sr.n_slots + FOLD_GROUP - 1) / FOLD_GROUP;
-          sr.slot_stride = FOLD_GROUP;
-        }
-        sp.push_back(sr);
-      } else {
-        tk.push_back(Task{static_cast<int32_t>(r), b, e, -1});
-      }
-    }
-    {  // longest first, ties in list order: a counting sort by length (stable, O(n + max length))
-      int32_t max_len = 0;
-      for (const Task &a : tk) max_len = std::max(max_len, a.end - a.begin);
-      std::vector<int32_t> start(static_cast<size_t>(max_len) + 2, 0);
-      for (const Task &a : tk) start[max_len - (a.end - a.begin) + 1]++;
-      for (size_t i = 1; i < start.size(); i++) start[i] += start[i - 1];
-      std::vector<Task> sorted(tk.size());
-      for (const Task &a : tk) sorted[start[max_len - (a.end - a.begin)]++] = a;
-      tk.swap(sorted);
-    }
-    // (dealing length strata round-robin so that neighbouring waves sit in different phases
-    // was tried: 3-5 % slower, and 2x slower when the stratum count shares a factor with the
-    // 8 XCDs the dispatcher deals workgroups to - longest-first keeps the XCDs balanced)
-    std::stable_sort(sp.begin(), sp.end(),
-                     [](const SplitRow &a, const SplitRow &b) { return a.n_slots > b.n_slots; });
-    n_tasks = static_cast<int32_t>(tk.size());
-    n_split = static_cast<int32_t>(sp.size());
-    n_short = n_short16 = n_short8 = 0;
-    while (n_short < n_tasks && tk[n_tasks - 1 - n_short].slot < 0 &&
-           tk[n_tasks - 1 - n_short].end - tk[n_tasks - 1 - n_short].begin <= SHORT_MAX) {
-      if (tk[n_tasks - 1 - n_short].end - tk[n_tasks - 1 - n_short].begin <= 16) n_short16++;
-      if (tk[n_tasks - 1 - n_short].end - tk[n_tasks - 1 - n_short].begin <= 8) n_short8++;
-      n_short++;
-    }
-    long_entries = 0;  // entries of the tasks in front of the short ones (the rank-update kernels' work)
-    for (int32_t i = 0; i < n_tasks - n_short; i++) long_entries += tk[i].end - tk[i].begin;
-    n_slots = slots;
+    const TaskPlan pl = plan_tasks(ip32.data(), m.rows, m.cols, rb, re, cfg, CH, chunk_long);
+    static_cast<PlanCounts &>(*this) = pl;
     if (share) {
       indptr.borrow(share->indptr);
       indices.borrow(share->indices);
       data.borrow(share->data);
+      reg.borrow(share->reg);
     } else {
       if (!indptr_ready) indptr.upload(ip32, s);
       if (!entries_ready) upload_entries(m, s);
+      reg.upload(pl.reg, s);
     }
-    {
-      std::vector<int32_t> order(re - rb);
-      {  // rows by length, longest first, ties in row order (counting sort)
-        int32_t max_len = 0;
-        for (int64_t r = rb; r < re; r++) max_len = std::max(max_len, ip32[r + 1] - ip32[r]);
-        std::vector<int32_t> start(static_cast<size_t>(max_len) + 2, 0);
-        for (int64_t r = rb; r < re; r++) start[max_len - (ip32[r + 1] - ip32[r]) + 1]++;
-        for (size_t i = 1; i < start.size(); i++) start[i] += start[i - 1];
-        for (int64_t r = rb; r < re; r++)
-          order[start[max_len - (ip32[r + 1] - ip32[r])]++] = static_cast<int32_t>(r);
-      }
-      rows_by_len.upload(order, s);
-      if (cfg.K > 128 && cfg.K <= 256) {  // the classes of the matrix-free CG kernels
-        size_t i = 0;
-        for (int c = 0; c < MF_CLASSES; c++) {
-          mf_class[c] = static_cast<int32_t>(i);
-          const int32_t lower = c + 1 < MF_CLASSES ? MF_CAPS[c + 1] : -1;  // class c: lower < length <= MF_CAPS[c]
-          while (i < order.size() && ip32[order[i] + 1] - ip32[order[i]] > lower) i++;
-        }
-        mf_class[MF_CLASSES] = static_cast<int32_t>(order.size());
-        std::vector<MfLongRow> lr;
-        std::vector<MfChunk> ch;
-        for (int32_t k = 0; k < mf_class[1]; k++) {
-          const int32_t r = order[k], b = ip32[r], e = ip32[r + 1], nz = e - b;
-          const int32_t nch = (nz + MF_CHUNK - 1) / MF_CHUNK;
-          const int32_t per = (((nz + nch - 1) / nch) + 15) & ~15;  // whole 16-entry groups
-          MfLongRow L{r, static_cast<int32_t>(ch.size()), 0, 0};
-          for (int32_t c = b; c < e; c += per) {
-            ch.push_back(MfChunk{k, c, std::min(c + per, e), 0});
-            L.n_chunks++;
-          }
-          lr.push_back(L);
-        }
-        mf_n_lrows = static_cast<int32_t>(lr.size());
-        mf_n_chunks = static_cast<int32_t>(ch.size());
-        mf_lrows.upload(lr, s);
-        mf_chunks.upload(ch, s);
-        IRS_HIP(hipStreamSynchronize(s));
-      }
-      n_long = 0;  // rows long enough for a whole workgroup (ialspp_long_kernel)
-      while (n_long < static_cast<int32_t>(order.size()) &&
-             ip32[order[n_long] + 1] - ip32[order[n_long]] > 2048)
-        n_long++;
+    rows_by_len.upload(pl.rows_by_len, s);
+    if (cfg.K > 128 && cfg.K <= 256) {  // the classes of the matrix-free CG kernels
+      mf_lrows.upload(pl.mf_lrows, s);
+      mf_chunks.upload(pl.mf_chunks, s);
     }
-    if (share) reg.borrow(share->reg);
-    else reg.upload(regs, s);
-    tasks.upload(tk, s);
-    split.upload(sp, s);
-    n_fold = static_cast<int32_t>(fg.size());
-    fold.upload(fg, s);
+    tasks.upload(pl.tasks, s);
+    split.upload(pl.split, s);
+    fold.upload(pl.fold, s);
     IRS_HIP(hipStreamSynchronize(s));  // host vectors go out of scope
+  }
+};
+
+// A stream for work beside another one, created on first use: fork(from) makes it wait for what `from` holds so
+// far and returns it, join(to) makes `to` wait for what it holds.
+struct BesideStream {
+  hipStream_t s = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  hipStream_t fork(hipStream_t from) {
+    if (!s) {
+      IRS_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+      IRS_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
+      IRS_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
+    }
+    IRS_HIP(hipEventRecord(ev_fork, from));
+    IRS_HIP(hipStreamWaitEvent(s, ev_fork, 0));
+    return s;
+  }
+  void join(hipStream_t to) {
+    IRS_HIP(hipEventRecord(ev_join, s));
+    IRS_HIP(hipStreamWaitEvent(to, ev_join, 0));
+  }
+  void destroy() {
+    if (!s) return;
+    (void)hipStreamSynchronize(s);
+    (void)hipStreamDestroy(s);
+    (void)hipEventDestroy(ev_fork);
+    (void)hipEventDestroy(ev_join);
   }
 };
 
@@ -372,16 +276,14 @@ struct Profiler {
 using namespace irs;
 using namespace irs::ials;
 
-struct irs_ials_trainer {
+struct irs_ials_trainer : irs::ials::Switches {  // (opt_*: read_switches())
   irs_ials_model_config cfg;
   int64_t K = 0, n_users = 0, n_items = 0;
   int KP = 0, T = 0;
   int device = 0;
   hipStream_t stream = nullptr;
-  hipStream_t stream2 = nullptr;  // iALS++: the short-row launch beside the long-row launch
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  hipStream_t stream3 = nullptr;  // eigenbasis short rows: every other pass
-  hipEvent_t ev_fork3 = nullptr, ev_join3 = nullptr;
+  BesideStream beside;   // beside `stream`: short rows beside long rows, the eigen-decomposition (fork() / join())
+  BesideStream beside3;  // beside that one: every other pass of the eigenbasis short rows
   bool has_X = false;
   bool whole = true;  // unsharded: both CSR orientations are complete on this device
   irs_ials_shard shard{0, 0, 0, 0};
@@ -416,11 +318,9 @@ struct irs_ials_trainer {
   int *eig_resident = nullptr;  // host-pinned: the decomposition kernel reports that it has a CU
   int eig_token = 0;
   float eig_stats_host[4] = {0, 0, 0, 0};
-  bool opt_eig = true;  // IRSPACK_AMD_IALS_EIG
   // matrix-free CG at 128 < K <= 256 (ials_mf_kernels.hpp): state of the level-synchronous rows
   DeviceBuffer<float> mf_vec, mf_xs, mf_rs, mf_partial, mf_r2;
   DeviceBuffer<int32_t> mf_done;
-  bool opt_mf = true;   // IRSPACK_AMD_IALS_MF
   // irs_ials_sharded_step: the Gramian of side s has been all-reduced ahead of its half-epoch
   bool gram_prefetched[2] = {false, false};
   // ... and the rows of the shard cut into chunks that are solved and exchanged one after the
@@ -429,56 +329,48 @@ struct irs_ials_trainer {
   int32_t eig_last = 0; // 1: the last half-step took the eigenbasis path (diagnostics)
   bool gk() const { return KP > 256; }   // K > 256: every size is a run-time value
   Profiler prof;
-  bool opt_wave128 = true, opt_unit = true, opt_short = true, opt_wg16 = true;  // read_switches()
-  bool opt_short2 = true;  // two short rows per wave (IRSPACK_AMD_IALS_SHORT2)
-  bool opt_pp_direct = true;  // iALS++ with one block = the direct solve (IRSPACK_AMD_IALSPP_DIRECT)
-  bool opt_pp_chain = true;   // iALS++ prediction passes merged into the rank updates (IRSPACK_AMD_IALSPP_CHAIN)
-  bool opt_pp_fork = true;    // iALS++ short-row launch on a second stream (IRSPACK_AMD_IALSPP_FORK)
-  bool opt_bf16x3 = false;
+
+  int n_cu = 0;  // compute units of `device`
 
   int64_t rows_of(int which) const { return which == 0 ? n_users : n_items; }
+  // the constant every stored entry adds to its confidence (hpp:190-191, 431-432)
+  float bias() const { return cfg.loss_type == IRS_LOSS_IALSPP ? 0.0f : cfg.alpha0; }
+  hipStream_t fork() { return beside.fork(stream); }
+  void join() { beside.join(stream); }
+  // where the iALS++ kernels write the LLT status that the reference does not test (hpp:495-497)
+  int32_t *llt_sink() {
+    if (!pp_llt_sink.ptr) {
+      pp_llt_sink.alloc(1);
+      pp_llt_sink.zero(stream);
+    }
+    return pp_llt_sink.ptr;
+  }
 };
 
 namespace {
 
 // T = KP / 16.  T <= 4: one wave per row (ials_kernels.hpp); T = 8 / 12 / 16: one
 // workgroup per row (ials_wg_kernels.hpp).
-#define IRS_DISPATCH_T(t, ...)                                                      \
-  switch (t) {                                                                      \
-    case 1: { constexpr int TT = 1; __VA_ARGS__; } break;                           \
-    case 2: { constexpr int TT = 2; __VA_ARGS__; } break;                           \
-    case 4: { constexpr int TT = 4; __VA_ARGS__; } break;                           \
-    default:                                                                        \
-      throw std::invalid_argument("irspack_amd: unsupported padded latent dimension."); \
-  }
-#define IRS_DISPATCH_T8(t, ...)                                                     \
-  switch (t) {                                                                      \
-    case 1: { constexpr int TT = 1; __VA_ARGS__; } break;                           \
-    case 2: { constexpr int TT = 2; __VA_ARGS__; } break;                           \
-    case 4: { constexpr int TT = 4; __VA_ARGS__; } break;                           \
-    case 8: { constexpr int TT = 8; __VA_ARGS__; } break;                           \
-    default:                                                                        \
-      throw std::invalid_argument("irspack_amd: unsupported padded latent dimension."); \
-  }
-#define IRS_DISPATCH_TW(t, ...)                                                     \
-  switch (t) {                                                                      \
-    case 8: { constexpr int TT = 8; __VA_ARGS__; } break;                           \
-    case 12: { constexpr int TT = 12; __VA_ARGS__; } break;                         \
-    case 16: { constexpr int TT = 16; __VA_ARGS__; } break;                         \
-    default:                                                                        \
-      throw std::invalid_argument("irspack_amd: unsupported padded latent dimension."); \
-  }
-#define IRS_DISPATCH_ANY(t, ...)                                                    \
-  switch (t) {                                                                      \
-    case 1: { constexpr int TT = 1; __VA_ARGS__; } break;                           \
-    case 2: { constexpr int TT = 2; __VA_ARGS__; } break;                           \
-    case 4: { constexpr int TT = 4; __VA_ARGS__; } break;                           \
-    case 8: { constexpr int TT = 8; __VA_ARGS__; } break;                           \
-    case 12: { constexpr int TT = 12; __VA_ARGS__; } break;                         \
-    case 16: { constexpr int TT = 16; __VA_ARGS__; } break;                         \
-    default:                                                                        \
-      throw std::invalid_argument("irspack_amd: unsupported padded latent dimension."); \
-  }
+#define IRS_T_CASE(n, ...) case n: { constexpr int TT = n; __VA_ARGS__; } break;
+#define IRS_T_OTHER default: throw std::invalid_argument("irspack_amd: unsupported padded latent dimension.");
+#define IRS_DISPATCH_T(t, ...) \
+  switch (t) { IRS_T_CASE(1, __VA_ARGS__) IRS_T_CASE(2, __VA_ARGS__) IRS_T_CASE(4, __VA_ARGS__) IRS_T_OTHER }
+#define IRS_DISPATCH_T8(t, ...) \
+  switch (t) { IRS_T_CASE(1, __VA_ARGS__) IRS_T_CASE(2, __VA_ARGS__) IRS_T_CASE(4, __VA_ARGS__) IRS_T_CASE(8, __VA_ARGS__) IRS_T_OTHER }
+#define IRS_DISPATCH_TW(t, ...) \
+  switch (t) { IRS_T_CASE(8, __VA_ARGS__) IRS_T_CASE(12, __VA_ARGS__) IRS_T_CASE(16, __VA_ARGS__) IRS_T_OTHER }
+#define IRS_DISPATCH_ANY(t, ...)                                                                                  \
+  switch (t) { IRS_T_CASE(1, __VA_ARGS__) IRS_T_CASE(2, __VA_ARGS__) IRS_T_CASE(4, __VA_ARGS__) IRS_T_CASE(8, __VA_ARGS__) \
+               IRS_T_CASE(12, __VA_ARGS__) IRS_T_CASE(16, __VA_ARGS__) IRS_T_OTHER }
+
+// the eigenbasis kernels exist at KP = 64 and 128 (SolveRoute::eig_candidate admits no other)
+#define IRS_DISPATCH_EIG_KP(kp, ...)                    \
+  if ((kp) == 128) { constexpr int KPP = 128; __VA_ARGS__; } \
+  else { constexpr int KPP = 64; __VA_ARGS__; }
+// the matrix-free CG kernels exist at KP = 192 (T = 12) and 256
+#define IRS_DISPATCH_MF_KP(t, ...)                    \
+  if ((t) == 12) { constexpr int KPP = 192; __VA_ARGS__; } \
+  else { constexpr int KPP = 256; __VA_ARGS__; }
 
 void validate_config(const irs_ials_model_config &c) {
   check_arg(c.K >= 1, "K must be positive.");
@@ -493,6 +385,7 @@ void read_switches(irs_ials_trainer *t);
 
 void alloc_common(irs_ials_trainer *t) {
   read_switches(t);
+  IRS_HIP(hipDeviceGetAttribute(&t->n_cu, hipDeviceAttributeMultiprocessorCount, t->device));
   t->KP = padded_k(t->K);
   t->T = t->KP / 16;
   for (int w = 0; w < 2; w++) {
@@ -661,7 +554,7 @@ GkParams gk_params(irs_ials_trainer *t, Side &sd, const float *other, float *tar
   p.D = static_cast<int32_t>(t->K);
   p.Np = static_cast<int32_t>(ceil_div(t->K, 64) * 64);
   p.K = static_cast<int32_t>(t->K);
-  p.bias = t->cfg.loss_type == IRS_LOSS_IALSPP ? 0.0f : t->cfg.alpha0;
+  p.bias = t->bias();
   p.mode = 0;
   p.err_flag = t->err_flag.ptr;
   return p;
@@ -704,8 +597,7 @@ void launch_gk_solve(irs_ials_trainer *t, Side &sd, const float *other, float *t
   const int32_t n = p.n_rows;
   if (n <= 0) return;
   if (sc->solver_type == IRS_SOLVER_CG) {
-    const int steps = sc->max_cg_steps == 0 ? static_cast<int>(t->K)
-                                            : static_cast<int>(std::min<uint64_t>(sc->max_cg_steps, 1u << 20));
+    const int steps = cg_step_count(sc->max_cg_steps, t->K);
     const size_t lds = (4 * static_cast<size_t>(t->KP) + 8) * sizeof(float) +
                        4 * static_cast<size_t>(t->KP) * sizeof(double);  // vectors + float64 partial sums
     // a row's CG vectors live in the workgroup's LDS (160 KB per compute unit on gfx950): say so
@@ -735,16 +627,12 @@ void launch_gk_solve(irs_ials_trainer *t, Side &sd, const float *other, float *t
 void launch_ialspp_general(irs_ials_trainer *t, Side &sd, const float *other, float *target, int pidx,
                            const irs_ials_solver_config *sc) {
   GkParams base = gk_params(t, sd, other, target, pidx, nullptr);
-  if (!t->pp_llt_sink.ptr) {
-    t->pp_llt_sink.alloc(1);
-    t->pp_llt_sink.zero(t->stream);
-  }
-  base.err_flag = t->pp_llt_sink.ptr;  // the reference does not test the LLT status here (hpp:495-497)
+  base.err_flag = t->llt_sink();
   const int32_t n = base.n_rows;
   if (n <= 0) return;
   t->pp_pred.alloc(static_cast<size_t>(sd.nnz) + 320);
   const int32_t K = static_cast<int32_t>(t->K);
-  const int32_t sub = static_cast<int32_t>(std::min<uint64_t>(std::max<uint64_t>(1, sc->ialspp_subspace_dimension), t->K));
+  const int32_t sub = pp_variant(sc->ialspp_subspace_dimension, t->K, t->KP, t->opt_pp_chain).sub;
   base.mode = 1;
   base.pred = t->pp_pred.ptr;
   for (uint64_t it = 0; it < sc->ialspp_iteration; it++) {
@@ -790,15 +678,12 @@ void launch_ialspp(irs_ials_trainer *t, Side &sd, const float *other, float *tar
   if (n_rows <= 0) return;
   // blocks wider than 64 dims: run-time sizes (ials_gk_kernels.hpp).  Blocks up to 64 dims keep
   // the tuned kernels at every K: they only hold the x row (KP floats) per wave beyond the block.
-  if (sc->ialspp_subspace_dimension > 64 || t->KP > 2048) {
+  const PpVariant v = pp_variant(sc->ialspp_subspace_dimension, t->K, t->KP, t->opt_pp_chain);
+  if (v.general) {
     launch_ialspp_general(t, sd, other, target, pidx, sc);
     return;
   }
   t->pp_pred.alloc(static_cast<size_t>(sd.nnz) + 320);
-  if (!t->pp_llt_sink.ptr) {
-    t->pp_llt_sink.alloc(1);
-    t->pp_llt_sink.zero(t->stream);
-  }
   PpParams p;
   p.indptr = sd.indptr.ptr;
   p.indices = sd.indices.ptr;
@@ -810,26 +695,22 @@ void launch_ialspp(irs_ials_trainer *t, Side &sd, const float *other, float *tar
   p.reg = sd.reg.ptr;
   p.P = t->P[pidx].ptr;
   p.pred = t->pp_pred.ptr;
-  p.ignored_flag = t->pp_llt_sink.ptr;
-  p.bias = t->cfg.loss_type == IRS_LOSS_IALSPP ? 0.0f : t->cfg.alpha0;  // hpp:431-432
+  p.ignored_flag = t->llt_sink();
+  p.bias = t->bias();
   p.K = static_cast<int32_t>(t->K);
   p.KP = t->KP;
   p.xs_extra = std::max(0, t->KP - 256);
-  // a subspace dimension of 0 or 1 is the iCD branch (hpp:673-677)
-  p.sub = static_cast<int32_t>(std::max<uint64_t>(1, sc->ialspp_subspace_dimension));
+  p.sub = v.sub;
   p.zero_start = 0;
   p.chain = t->opt_pp_chain ? 1 : 0;
   p.P_blk = nullptr;
-  if (p.chain && p.sub == 64 && p.K > 64) {  // the blocks of P in accumulator layout
+  if (v.chained) {  // the blocks of P in accumulator layout
     const int nb = (p.K + 63) / 64;
     t->pp_pblk.alloc(static_cast<size_t>(nb) * 10 * 256);
     hipLaunchKernelGGL(pp_pack_p_kernel, dim3(nb), dim3(64), 0, t->stream, t->P[pidx].ptr, p.K, p.KP,
                        t->pp_pblk.ptr);
     p.P_blk = t->pp_pblk.ptr;
   }
-  const int D = std::min<int>(p.sub, p.K);
-  const int TS = D <= 16 ? 1 : D <= 32 ? 2 : 4;
-  const bool aligned = p.sub % TS == 0;
   // rows above 2048 stored entries get a whole workgroup each (they come first in
   // rows_by_len), the rest one wave each
   const int32_t n_long = std::min(sd.n_long, n_rows);
@@ -843,21 +724,11 @@ void launch_ialspp(irs_ials_trainer *t, Side &sd, const float *other, float *tar
                                 static_cast<int>(lds_long)));
     // The two launches touch different rows.  The long-row launch ends with a tail (a few rows
     // of 10^5 entries on a few CUs), so the one-wave-per-row launch runs beside it on a second
-    // stream (fork / join by events) instead of behind it.
+    // stream instead of behind it.
     const bool fork = n_long > 0 && n_rows > n_long && t->opt_pp_fork;
-    if (fork && !t->stream2) {
-      IRS_HIP(hipStreamCreateWithFlags(&t->stream2, hipStreamNonBlocking));
-      IRS_HIP(hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming));
-      IRS_HIP(hipEventCreateWithFlags(&t->ev_join, hipEventDisableTiming));
-    }
     for (uint64_t it = 0; it < sc->ialspp_iteration; it++) {
       t->prof.begin(kNames[pidx], t->stream);
-      hipStream_t s2 = t->stream;
-      if (fork) {
-        s2 = t->stream2;
-        IRS_HIP(hipEventRecord(t->ev_fork, t->stream));
-        IRS_HIP(hipStreamWaitEvent(s2, t->ev_fork, 0));
-      }
+      const hipStream_t s2 = fork ? t->fork() : t->stream;
       if (n_long > 0) {
         PpParams pl = p;
         pl.n_rows = n_long;
@@ -870,39 +741,27 @@ void launch_ialspp(irs_ials_trainer *t, Side &sd, const float *other, float *tar
         ps.n_rows = n_rows - n_long;
         hipLaunchKernelGGL(kernel, dim3(ceil_div(ps.n_rows, 4)), dim3(256), lds, s2, ps);
       }
-      if (fork) {
-        IRS_HIP(hipEventRecord(t->ev_join, s2));
-        IRS_HIP(hipStreamWaitEvent(t->stream, t->ev_join, 0));
-      }
+      if (fork) t->join();
       t->prof.end(t->stream);
     }
   };
-  // the form of the sweep is a template parameter (each form gets its own register budget)
-  const bool single = p.sub >= p.K;
-  const bool chained = !single && TS == 4 && aligned && p.chain && p.sub == 64 && p.K > 64;
-#define IRS_PP_LAUNCH(TSV, AL)                                                                        \
-  do {                                                                                                \
-    if (single)                                                                                       \
-      launch(ialspp_long_kernel<TSV, AL, 1>, PpLongGeo<TSV>::LDS_FLOATS, ialspp_kernel<TSV, AL, 1>,   \
-             PpGeo<TSV>::LDS_FLOATS);                                                                 \
-    else                                                                                              \
-      launch(ialspp_long_kernel<TSV, AL, 0>, PpLongGeo<TSV>::LDS_FLOATS, ialspp_kernel<TSV, AL, 0>,   \
-             PpGeo<TSV>::LDS_FLOATS);                                                                 \
+  // the form of the sweep is a template parameter (each form gets its own register budget): 0 = blocks,
+  // 1 = one block, 2 = chained blocks (instantiated at <4, true> only)
+#define IRS_PP_LAUNCH(TSV, AL, FORM)                                                                      \
+  launch(ialspp_long_kernel<TSV, AL, FORM>, PpLongGeo<TSV>::LDS_FLOATS, ialspp_kernel<TSV, AL, FORM>,     \
+         PpGeo<TSV>::LDS_FLOATS)
+#define IRS_PP_FORMS(TSV, AL)              \
+  do {                                     \
+    if (v.single) IRS_PP_LAUNCH(TSV, AL, 1); \
+    else IRS_PP_LAUNCH(TSV, AL, 0);        \
   } while (0)
-  switch (TS * 2 + (aligned ? 1 : 0)) {
-    case 2:  // TS = 1 is always aligned
-    case 3: IRS_PP_LAUNCH(1, true); break;
-    case 4: IRS_PP_LAUNCH(2, false); break;
-    case 5: IRS_PP_LAUNCH(2, true); break;
-    case 8: IRS_PP_LAUNCH(4, false); break;
-    default:
-      if (chained)
-        launch(ialspp_long_kernel<4, true, 2>, PpLongGeo<4>::LDS_FLOATS, ialspp_kernel<4, true, 2>,
-               PpGeo<4>::LDS_FLOATS);
-      else
-        IRS_PP_LAUNCH(4, true);
-      break;
-  }
+  if (v.TS == 1) IRS_PP_FORMS(1, true);  // (one tile is always aligned)
+  else if (v.TS == 2 && !v.aligned) IRS_PP_FORMS(2, false);
+  else if (v.TS == 2) IRS_PP_FORMS(2, true);
+  else if (!v.aligned) IRS_PP_FORMS(4, false);
+  else if (v.chained) IRS_PP_LAUNCH(4, true, 2);
+  else IRS_PP_FORMS(4, true);
+#undef IRS_PP_FORMS
 #undef IRS_PP_LAUNCH
   IRS_HIP(hipGetLastError());
 }
@@ -947,52 +806,29 @@ void launch_eigen(irs_ials_trainer *t, int pidx, hipStream_t stream) {
   const int warm = t->eig_warm[pidx] ? 1 : 0;
   t->eig_warm[pidx] = true;
   const size_t lds = static_cast<size_t>(KP) * KP * sizeof(double);
-  auto launch = [&](auto kernel) {
-    IRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+  IRS_DISPATCH_EIG_KP(KP, {
+    IRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(eig_jacobi_kernel<KPP>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
     t->prof.begin("eig_jacobi", stream);
-    hipLaunchKernelGGL(kernel, dim3(1), dim3(1024), lds, stream,
+    hipLaunchKernelGGL(eig_jacobi_kernel<KPP>, dim3(1), dim3(1024), lds, stream,
                        static_cast<const float *>(t->P[pidx].ptr), static_cast<int>(t->K), o, warm);
     t->prof.end(stream);
-  };
-  if (KP == 128) launch(eig_jacobi_kernel<128>);
-  else launch(eig_jacobi_kernel<64>);
+  });
   IRS_HIP(hipGetLastError());
 }
 
 // Short rows (<= 32 stored entries, the tail of the task list) in the eigenbasis of P
 // (ials_eig_kernels.hpp), on a SECOND stream beside the kernels of the longer rows: the
 // eigen-decomposition is one workgroup (1 - 3 ms of one CU) and must not leave the other 255 idle.
-//   eig_begin   decides from host-side facts whether the path is a candidate and, if so, forks the
-//               second stream and starts the decomposition + the copy of its statistics;
+//   eig_begin   (the route found the side a candidate, SolveRoute::eig_candidate) forks the second
+//               stream and starts the decomposition + the copy of its statistics;
 //   eig_finish  (after the caller has launched the long rows on the main stream) waits for the
 //               statistics, checks the conditioning, runs table product / short-row kernels /
 //               rotation on the second stream and joins it.  Returns false - nothing launched
 //               that changes the factors - when the path declines; the caller then runs its
 //               usual kernels over those rows.
-bool eig_begin(irs_ials_trainer *t, Side &sd, int pidx, bool cg) {
-  t->eig_last = 0;
-  const int KP = t->KP;
-  if (!t->opt_eig || (KP != 64 && KP != 128) || !sd.positive || sd.n_short <= 0) return false;
-  // worth one eigen-decomposition (milliseconds of ONE compute unit) and the product that takes
-  // every gathered row into the eigenbasis (n_other x KP x KP multiply-adds, 8 KP bytes per row)?
-  // configs[3]: the user side (9.7 M short rows, 10^6 gathered rows) yes, the item side (0.8 M
-  // short rows, 10^7 gathered rows: the product alone would cost more than those rows) no.
-  if (static_cast<double>(sd.n_short) * KP * KP * KP < 3e11) return false;
-  // Cholesky saves a dense KP^3 / 3 factorisation per short row, CG only its products with P, and
-  // the table product competes with the long rows' kernels beside it.  configs[3], item side
-  // (0.8 M short rows, 10^7 gathered rows) on this path: Cholesky epoch 60.2 -> 52.1 ms, CG epoch
-  // 48.8 -> 50.9 ms.
-  const double ratio = cg ? 64.0 : 8.0;
-  if (static_cast<double>(sd.n_short) * KP < ratio * static_cast<double>(sd.n_other)) return false;
-  if (!t->stream2) {
-    IRS_HIP(hipStreamCreateWithFlags(&t->stream2, hipStreamNonBlocking));
-    IRS_HIP(hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming));
-    IRS_HIP(hipEventCreateWithFlags(&t->ev_join, hipEventDisableTiming));
-  }
-  IRS_HIP(hipEventRecord(t->ev_fork, t->stream));  // (the Gramian of this half-step is on t->stream)
-  IRS_HIP(hipStreamWaitEvent(t->stream2, t->ev_fork, 0));
-  launch_eigen(t, pidx, t->stream2);
+void eig_begin(irs_ials_trainer *t, int pidx) {
+  launch_eigen(t, pidx, t->fork());  // (the Gramian of this half-step is on t->stream)
   // the decomposition needs a CU to itself (its LDS): the long rows' kernels, which the caller
   // launches next, must not reach the device before it is resident.  It reports that through a
   // host-pinned word; the wait is the time the stream's earlier work (the Gramian) still needs,
@@ -1014,33 +850,28 @@ bool eig_begin(irs_ials_trainer *t, Side &sd, int pidx, bool cg) {
       fprintf(stderr, "irspack_amd: the eigen-decomposition kernel did not report residency within 200 ms "
                       "(side %d); the long rows' kernels are launched without waiting for it\n", pidx);
   }
-  return true;
 }
 
 bool eig_finish(irs_ials_trainer *t, Side &sd, const float *other, float *target, int pidx, bool cg,
                 int max_cg_steps, int32_t *err_flag) {
   const int KP = t->KP;
-  hipStream_t s2 = t->stream2;
+  hipStream_t s2 = t->beside.s;
   IRS_HIP(hipMemcpyAsync(t->eig_stats_host, t->eig_stats.ptr, 3 * sizeof(float), hipMemcpyDeviceToHost, s2));
   IRS_HIP(hipStreamSynchronize(s2));
-  const float *st = t->eig_stats_host;
-  // M = P + reg_r I must be well conditioned for EVERY row: float32 carries Q and 1 / (lambda + reg)
-  const double lo = std::max(0.0, static_cast<double>(st[1])) + sd.reg_min;
-  const double hi = static_cast<double>(st[0]) + sd.reg_min;
-  if (!(lo > 0.0) || !(hi <= 1e4 * lo) || !std::isfinite(hi)) return false;
+  if (!eig_well_conditioned(t->eig_stats_host[0], t->eig_stats_host[1], sd.reg_min)) return false;
   // V~ = other Q  (every gathered row once per half-step)
   const int64_t n_other = sd.n_other;
   t->eig_table.alloc(static_cast<size_t>(std::max<int64_t>(n_other, 1)) * KP);
   check_arg(n_other < (int64_t(1) << 31) - 64, "eigenbasis table: too many gathered rows");
+  hipStream_t sb = s2;
+  // dst[dst_rows] = src[src_rows] M^T over n rows (null rows: the n first), on the stream of the current pass
+  auto rotate = [&](const float *src, const Task *src_rows, float *dst, const Task *dst_rows, const float *M,
+                    int64_t n) {
+    IRS_DISPATCH_EIG_KP(KP, hipLaunchKernelGGL((rows_times_matT_kernel<KPP>), dim3(ceil_div(n, 256)), dim3(256),
+                                               0, sb, src, src_rows, dst, dst_rows, M, static_cast<int>(n)));
+  };
   t->prof.begin("eig_table", s2);
-  if (KP == 128)
-    hipLaunchKernelGGL((rows_times_matT_kernel<128>), dim3(ceil_div(n_other, 256)), dim3(256), 0, s2, other,
-                       static_cast<const Task *>(nullptr), t->eig_table.ptr, static_cast<const Task *>(nullptr),
-                       static_cast<const float *>(t->eig_Qrows.ptr), static_cast<int>(n_other));
-  else
-    hipLaunchKernelGGL((rows_times_matT_kernel<64>), dim3(ceil_div(n_other, 256)), dim3(256), 0, s2, other,
-                       static_cast<const Task *>(nullptr), t->eig_table.ptr, static_cast<const Task *>(nullptr),
-                       static_cast<const float *>(t->eig_Qrows.ptr), static_cast<int>(n_other));
+  rotate(other, nullptr, t->eig_table.ptr, nullptr, t->eig_Qrows.ptr, n_other);
   t->prof.end(s2);
   const int32_t first = sd.n_tasks - sd.n_short;
   // rows per pass: x~ scratch of B x KP floats (IRSPACK_AMD_IALS_EIG_PASS_ROWS: tests shrink it)
@@ -1054,7 +885,7 @@ bool eig_finish(irs_ials_trainer *t, Side &sd, const float *other, float *target
   p.lam = t->eig_lam.ptr;
   p.reg = sd.reg.ptr;
   p.xt = t->eig_xt.ptr;
-  p.bias = t->cfg.loss_type == IRS_LOSS_IALSPP ? 0.0f : t->cfg.alpha0;
+  p.bias = t->bias();
   p.K = static_cast<int32_t>(t->K);
   p.max_cg_steps = max_cg_steps;
   p.warm_start = 1;
@@ -1062,45 +893,25 @@ bool eig_finish(irs_ials_trainer *t, Side &sd, const float *other, float *target
   // passes alternate between two streams (each with its own x~ scratch): the rotation of one pass
   // (matrix cores, streaming) runs beside the short-row kernel of the next (gather latency)
   const bool two = sd.n_short > B;
-  hipStream_t sb = s2;
   float *xt = t->eig_xt.ptr;
   if (two) {
     t->eig_xt2.alloc(static_cast<size_t>(B) * KP);
-    if (!t->stream3) {
-      IRS_HIP(hipStreamCreateWithFlags(&t->stream3, hipStreamNonBlocking));
-      IRS_HIP(hipEventCreateWithFlags(&t->ev_fork3, hipEventDisableTiming));
-      IRS_HIP(hipEventCreateWithFlags(&t->ev_join3, hipEventDisableTiming));
-    }
-    IRS_HIP(hipEventRecord(t->ev_fork3, s2));  // (after the table product)
-    IRS_HIP(hipStreamWaitEvent(t->stream3, t->ev_fork3, 0));
+    t->beside3.fork(s2);  // (after the table product)
   }
-  auto rotate = [&](const float *src, const Task *src_rows, float *dst, const Task *dst_rows, const float *M,
-                    int n) {
-    if (KP == 128)
-      hipLaunchKernelGGL((rows_times_matT_kernel<128>), dim3(ceil_div(n, 256)), dim3(256), 0, sb, src,
-                         src_rows, dst, dst_rows, M, n);
-    else
-      hipLaunchKernelGGL((rows_times_matT_kernel<64>), dim3(ceil_div(n, 256)), dim3(256), 0, sb, src,
-                         src_rows, dst, dst_rows, M, n);
-  };
   const char *kname = cg ? (pidx == 0 ? "ials_short_cg_user" : "ials_short_cg_item")
                          : (pidx == 0 ? "ials_short_cholesky_user" : "ials_short_cholesky_item");
-  // the list is longest first: [17..32 entries | 9..16 entries | <= 8 entries]
-  const int32_t n32 = sd.n_short - sd.n_short16;
-  constexpr bool rows8 = true;  // (the 8-entry forms: four waves per SIMD for the tail of the list)
-  const int32_t n16 = sd.n_short - (rows8 ? sd.n_short8 : 0);         // rows before the <= 8 class
   for (int32_t b0 = 0; b0 < sd.n_short; b0 += B) {
     const int32_t m = std::min(B, sd.n_short - b0);
     const Task *tasks = sd.tasks.ptr + first + b0;
     const bool odd = two && ((b0 / B) & 1);
-    sb = odd ? t->stream3 : s2;
+    sb = odd ? t->beside3.s : s2;
     xt = odd ? t->eig_xt2.ptr : t->eig_xt.ptr;
     p.tasks = tasks;
     p.n_tasks = m;
-    // rows of this pass with 17..32 entries: [0, m2) (one row per wave), the rest have <= 16
-    // (four rows per wave, 16 lanes each)
-    const int32_t m2 = std::max(0, std::min(b0 + m, n32) - b0);
-    const int32_t m3 = std::max(m2, std::min(b0 + m, n16) - b0);  // [m2, m3): 9..16 entries, [m3, m): <= 8
+    // [0, m2): 17..32 entries (one row per wave); [m2, m3): 9..16, [m3, m): <= 8 (four rows per wave, 16 lanes
+    // each; the 8-entry forms: four waves per SIMD for the tail of the list)
+    const EigCuts cut = eig_pass_cuts(b0, m, sd.n_short, sd.n_short16, sd.n_short8);
+    const int32_t m2 = cut.m2, m3 = cut.m3;
     auto part = [&](auto kernel, int32_t off, int32_t cnt, int rows_per_block, size_t lds) {
       if (cnt <= 0) return;
       EigShortParams q = p;
@@ -1118,16 +929,13 @@ bool eig_finish(irs_ials_trainer *t, Side &sd, const float *other, float *target
     t->prof.begin(kname, sb);
     if (cg) {
       if (!rows16) {
-        if (KP == 128) part(ials_cg_eig_short_kernel<128>, 0, m, 4, 0);
-        else part(ials_cg_eig_short_kernel<64>, 0, m, 4, 0);
-      } else if (KP == 128) {
-        part(ials_cg_eig16_kernel<128, 32>, 0, m2, 8, 0);   // 17..32 entries: 32 lanes per row
-        part(ials_cg_eig16_kernel<128, 16>, m2, m3 - m2, 16, 0);
-        part(ials_cg_eig16_kernel<128, 16, 8>, m3, m - m3, 16, 0);
+        IRS_DISPATCH_EIG_KP(KP, part(ials_cg_eig_short_kernel<KPP>, 0, m, 4, 0));
       } else {
-        part(ials_cg_eig16_kernel<64, 32>, 0, m2, 8, 0);
-        part(ials_cg_eig16_kernel<64, 16>, m2, m3 - m2, 16, 0);
-        part(ials_cg_eig16_kernel<64, 16, 8>, m3, m - m3, 16, 0);
+        IRS_DISPATCH_EIG_KP(KP, {
+          part(ials_cg_eig16_kernel<KPP, 32>, 0, m2, 8, 0);   // 17..32 entries: 32 lanes per row
+          part(ials_cg_eig16_kernel<KPP, 16>, m2, m3 - m2, 16, 0);
+          part(ials_cg_eig16_kernel<KPP, 16, 8>, m3, m - m3, 16, 0);
+        });
       }
     } else {
       const size_t lds1 = 4 * (Chol16Geo<1>::LDS_FLOATS + 32) * sizeof(float);
@@ -1136,38 +944,25 @@ bool eig_finish(irs_ials_trainer *t, Side &sd, const float *other, float *target
       // the register kernel is slower for Cholesky (its n x n factorisation is n^2 / 2 lane
       // broadcasts: configs[3] epoch 69 -> 77 ms) although it is the faster one for CG (68 -> 63)
       constexpr bool rows32 = false;
-      if (KP == 128) {
-        if (rows16 && rows32) part(ials_wb_eig16_kernel<128, 32>, 0, m2, 8, 0);
-        else part(ials_wb_short_kernel<128, 2>, 0, m2, 4, lds2);
+      IRS_DISPATCH_EIG_KP(KP, {
+        if (rows16 && rows32) part(ials_wb_eig16_kernel<KPP, 32>, 0, m2, 8, 0);
+        else part(ials_wb_short_kernel<KPP, 2>, 0, m2, 4, lds2);
         if (rows16) {
-          part(ials_wb_eig16_kernel<128, 16>, m2, m3 - m2, 16, 0);
-          part(ials_wb_eig16_kernel<128, 16, 8>, m3, m - m3, 16, 0);
+          part(ials_wb_eig16_kernel<KPP, 16>, m2, m3 - m2, 16, 0);
+          part(ials_wb_eig16_kernel<KPP, 16, 8>, m3, m - m3, 16, 0);
         } else {
-          part(ials_wb_short_kernel<128, 1>, m2, m - m2, 4, lds1);
+          part(ials_wb_short_kernel<KPP, 1>, m2, m - m2, 4, lds1);
         }
-      } else {
-        if (rows16 && rows32) part(ials_wb_eig16_kernel<64, 32>, 0, m2, 8, 0);
-        else part(ials_wb_short_kernel<64, 2>, 0, m2, 4, lds2);
-        if (rows16) {
-          part(ials_wb_eig16_kernel<64, 16>, m2, m3 - m2, 16, 0);
-          part(ials_wb_eig16_kernel<64, 16, 8>, m3, m - m3, 16, 0);
-        } else {
-          part(ials_wb_short_kernel<64, 1>, m2, m - m2, 4, lds1);
-        }
-      }
+      });
     }
     t->prof.end(sb);
     t->prof.begin("eig_rotate", sb);
     rotate(xt, nullptr, target, tasks, t->eig_Qcols.ptr, m);  // x = Q x~
     t->prof.end(sb);
   }
-  if (two) {
-    IRS_HIP(hipEventRecord(t->ev_join3, t->stream3));
-    IRS_HIP(hipStreamWaitEvent(s2, t->ev_join3, 0));
-  }
+  if (two) t->beside3.join(s2);
   IRS_HIP(hipGetLastError());
-  IRS_HIP(hipEventRecord(t->ev_join, s2));
-  IRS_HIP(hipStreamWaitEvent(t->stream, t->ev_join, 0));
+  t->join();
   t->eig_last = 1;
   return true;
 }
@@ -1186,25 +981,14 @@ void launch_mf_cg(irs_ials_trainer *t, Side &sd, const float *other, float *targ
   p.target = target;
   p.reg = sd.reg.ptr;
   p.P = t->P[pidx].ptr;
-  p.bias = t->cfg.loss_type == IRS_LOSS_IALSPP ? 0.0f : t->cfg.alpha0;  // hpp:190-191
+  p.bias = t->bias();
   p.K = static_cast<int32_t>(t->K);
-  p.max_cg_steps = sc->max_cg_steps == 0 ? static_cast<int32_t>(t->K)  // hpp:232-234
-                                         : static_cast<int32_t>(std::min<uint64_t>(sc->max_cg_steps, 1u << 20));
+  p.max_cg_steps = cg_step_count(sc->max_cg_steps, t->K);
   p.err_flag = t->err_flag.ptr;
   const int32_t n_long = sd.mf_n_lrows;
   static const bool fork_ok = env_flag("IRSPACK_AMD_MF_FORK", true);  // 0: one stream (A/B, profiling)
   const bool fork = fork_ok && n_long > 0 && sd.mf_class[MF_CLASSES] > sd.mf_class[1];
-  hipStream_t ls = t->stream;
-  if (fork) {
-    if (!t->stream2) {
-      IRS_HIP(hipStreamCreateWithFlags(&t->stream2, hipStreamNonBlocking));
-      IRS_HIP(hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming));
-      IRS_HIP(hipEventCreateWithFlags(&t->ev_join, hipEventDisableTiming));
-    }
-    IRS_HIP(hipEventRecord(t->ev_fork, t->stream));
-    IRS_HIP(hipStreamWaitEvent(t->stream2, t->ev_fork, 0));
-    ls = t->stream2;
-  }
+  const hipStream_t ls = fork ? t->fork() : t->stream;
   if (n_long > 0) {
     const size_t KP = static_cast<size_t>(t->KP);
     t->mf_vec.alloc(n_long * KP);
@@ -1243,8 +1027,7 @@ void launch_mf_cg(irs_ials_trainer *t, Side &sd, const float *other, float *targ
         }
       }
     };
-    if (t->T == 12) chain(mf_long_init_kernel<192>, mf_chunk_kernel<192>, mf_row_kernel<192>);
-    else chain(mf_long_init_kernel<256>, mf_chunk_kernel<256>, mf_row_kernel<256>);
+    IRS_DISPATCH_MF_KP(t->T, chain(mf_long_init_kernel<KPP>, mf_chunk_kernel<KPP>, mf_row_kernel<KPP>));
     t->prof.end(ls);
   }
   t->prof.begin(pidx == 0 ? "ials_solve_cg_user" : "ials_solve_cg_item", t->stream);
@@ -1258,24 +1041,18 @@ void launch_mf_cg(irs_ials_trainer *t, Side &sd, const float *other, float *targ
   };
   // classes 1 .. 4 of MF_CAPS: <= 320 (eight waves on one row), 160 (four), 80 (two rows of two
   // waves), 40 (four rows of one wave)
-  if (t->T == 12) {
-    resident(mf_cg_rows_kernel<192, 1, 8, MF_J>, 1, 1, 8);
-    resident(mf_cg_rows_kernel<192, 1, 4, MF_J>, 2, 1, 4);
-    resident(mf_cg_rows_kernel<192, 2, 2, MF_J>, 3, 2, 4);
-    resident(mf_cg_rows_kernel<192, 4, 1, MF_J>, 4, 4, 4);
-  } else {
-    resident(mf_cg_rows_kernel<256, 1, 8, MF_J>, 1, 1, 8);
-    resident(mf_cg_rows_kernel<256, 1, 4, MF_J>, 2, 1, 4);
-    resident(mf_cg_rows_kernel<256, 2, 2, MF_J>, 3, 2, 4);
-    resident(mf_cg_rows_kernel<256, 4, 1, MF_J>, 4, 4, 4);
-  }
+  IRS_DISPATCH_MF_KP(t->T, {
+    resident(mf_cg_rows_kernel<KPP, 1, 8, MF_J>, 1, 1, 8);
+    resident(mf_cg_rows_kernel<KPP, 1, 4, MF_J>, 2, 1, 4);
+    resident(mf_cg_rows_kernel<KPP, 2, 2, MF_J>, 3, 2, 4);
+    resident(mf_cg_rows_kernel<KPP, 4, 1, MF_J>, 4, 4, 4);
+  });
   t->prof.end(t->stream);
-  if (fork) {
-    IRS_HIP(hipEventRecord(t->ev_join, ls));
-    IRS_HIP(hipStreamWaitEvent(t->stream, t->ev_join, 0));
-  }
+  if (fork) t->join();
   IRS_HIP(hipGetLastError());
 }
+
+using SolveKernel = void (*)(SolveParams);
 
 // Solver::step (hpp:664-679) for side `s` over the rows of `sd`, writing `target`.
 void launch_solve(irs_ials_trainer *t, Side &sd, const float *other, float *target, int pidx,
@@ -1285,49 +1062,48 @@ void launch_solve(irs_ials_trainer *t, Side &sd, const float *other, float *targ
        {"ials_split_cholesky_user", "ials_split_cholesky_item"}},
       {{"ials_solve_cg_user", "ials_solve_cg_item"},
        {"ials_split_cg_user", "ials_split_cg_item"}}};
-  bool pp_direct = false;
-  if (sc->solver_type == IRS_SOLVER_IALSPP) {
-    if (prior)  // hpp:659-661
-      throw std::invalid_argument("Feature-aware iALS does not support IALSPP.");
-    // One block that covers every dimension (subspace dimension >= K, the default at K <= 64):
-    // the block step of hpp:436-502 is a Newton step of a quadratic, x - A^-1 (A x - b) with the
-    // A and b of step_cholesky (hpp:289-324; the gradient P x + reg x + sum (c (x.v - 1) - bias) v
-    // is A x - b).  It runs on the tuned rank-update + Cholesky kernel in the reference's own
-    // arithmetic FORM (round 5; RESID kernels, ials_kernels.hpp): the right-hand side is the
-    // negative gradient at the current row, built from the predictions v.x like hpp:455-474, the
-    // solve yields the step, the row moves by it.  (Rounds 2-4 computed the exact minimiser
-    // A^-1 b instead: the same number in exact arithmetic, but with kappa * 2^-24 of forward error
-    // where the reference's form has none - at the reference's DEFAULT alpha0 = 0 a row with
-    // fewer entries than K was up to 0.19 relative away from float64 where the reference is
-    // 3e-3, tests/test_gpu_operating_point.py.)  One sweep is then exactly the reference's; more
-    // sweeps repeat it like the reference does.  Like the reference on this path (hpp:495-497)
-    // a failed factorisation is not reported.
-    pp_direct = t->opt_pp_direct && sc->ialspp_subspace_dimension > 1 &&
-                static_cast<uint64_t>(sc->ialspp_subspace_dimension) >= t->K &&
-                sc->ialspp_iteration >= 1 && t->T <= 4 && target == t->factor[pidx].ptr;
-    if (!pp_direct) {
-      launch_ialspp(t, sd, other, target, pidx, sc);
-      return;
-    }
+  if (sc->solver_type == IRS_SOLVER_IALSPP && prior)  // hpp:659-661
+    throw std::invalid_argument("Feature-aware iALS does not support IALSPP.");
+  SolveFacts f;
+  static_cast<Switches &>(f) = *t;
+  f.T = t->T;
+  f.KP = t->KP;
+  f.K = t->K;
+  f.solver_type = sc->solver_type;
+  f.subspace_dimension = sc->ialspp_subspace_dimension;
+  f.sweeps = sc->ialspp_iteration;
+  f.has_prior = prior != nullptr;
+  f.other_own = other == t->factor[1 - pidx].ptr;
+  f.target_own = target == t->factor[pidx].ptr;
+  f.unit = sd.unit;
+  f.positive = sd.positive;
+  f.n_tasks = sd.n_tasks;
+  f.n_short = sd.n_short;
+  f.n_short16 = sd.n_short16;
+  f.n_other = sd.n_other;
+  f.long_entries = sd.long_entries;
+  f.zero_row = ceil_div(sd.n_other, 8) * 8;
+  const SolveRoute r = solve_route(f);
+  switch (r.path) {
+    case SolvePath::PP_BLOCKS:
+    case SolvePath::PP_GENERAL: launch_ialspp(t, sd, other, target, pidx, sc); return;
+    case SolvePath::GK: launch_gk_solve(t, sd, other, target, pidx, sc, prior, t->err_flag.ptr); return;
+    case SolvePath::MF_CG: launch_mf_cg(t, sd, other, target, pidx, sc); return;
+    case SolvePath::DENSE: break;
   }
-  if (t->gk()) {
-    int32_t *flag = t->err_flag.ptr;
-    if (pp_direct) {
-      if (!t->pp_llt_sink.ptr) {
-        t->pp_llt_sink.alloc(1);
-        t->pp_llt_sink.zero(t->stream);
-      }
-      flag = t->pp_llt_sink.ptr;
-    }
-    irs_ials_solver_config eff = *sc;
-    if (pp_direct) eff.solver_type = IRS_SOLVER_CHOLESKY;
-    launch_gk_solve(t, sd, other, target, pidx, &eff, prior, flag);
-    return;
-  }
-  if (sc->solver_type == IRS_SOLVER_CG && t->T > 8 && prior == nullptr && t->opt_mf) {
-    launch_mf_cg(t, sd, other, target, pidx, sc);
-    return;
-  }
+  // pp_direct - iALS++ with one block that covers every dimension (subspace dimension >= K, the default at
+  // K <= 64): the block step of hpp:436-502 is a Newton step of a quadratic, x - A^-1 (A x - b) with the
+  // A and b of step_cholesky (hpp:289-324; the gradient P x + reg x + sum (c (x.v - 1) - bias) v
+  // is A x - b).  It runs on the tuned rank-update + Cholesky kernel in the reference's own
+  // arithmetic FORM (round 5; RESID kernels, ials_kernels.hpp): the right-hand side is the
+  // negative gradient at the current row, built from the predictions v.x like hpp:455-474, the
+  // solve yields the step, the row moves by it.  (Rounds 2-4 computed the exact minimiser
+  // A^-1 b instead: the same number in exact arithmetic, but with kappa * 2^-24 of forward error
+  // where the reference's form has none - at the reference's DEFAULT alpha0 = 0 a row with
+  // fewer entries than K was up to 0.19 relative away from float64 where the reference is
+  // 3e-3, tests/test_gpu_operating_point.py.)  One sweep is then exactly the reference's; more
+  // sweeps repeat it like the reference does.  Like the reference on this path (hpp:495-497)
+  // a failed factorisation is not reported.
   SolveParams p;
   p.prior = prior;
   p.tasks = sd.tasks.ptr;
@@ -1341,25 +1117,12 @@ void launch_solve(irs_ials_trainer *t, Side &sd, const float *other, float *targ
   p.reg = sd.reg.ptr;
   p.P_acc = t->P_acc[pidx].ptr;
   p.P_accL = t->P_accL[pidx].ptr;
-  p.err_flag = t->err_flag.ptr;
-  if (pp_direct) {
-    if (!t->pp_llt_sink.ptr) {
-      t->pp_llt_sink.alloc(1);
-      t->pp_llt_sink.zero(t->stream);
-    }
-    p.err_flag = t->pp_llt_sink.ptr;
-  }
-  p.bias = t->cfg.loss_type == IRS_LOSS_IALSPP ? 0.0f : t->cfg.alpha0;  // hpp:190-191
+  p.err_flag = r.pp_direct ? t->llt_sink() : t->err_flag.ptr;
+  p.bias = t->bias();
   p.K = static_cast<int32_t>(t->K);
-  p.max_cg_steps = sc->max_cg_steps == 0 ? static_cast<int32_t>(t->K)
-                                         : static_cast<int32_t>(std::min<uint64_t>(
-                                               sc->max_cg_steps, 1u << 20));
+  p.max_cg_steps = cg_step_count(sc->max_cg_steps, t->K);
   p.warm_start = 1;
-  p.zero_row = static_cast<int32_t>(ceil_div(sd.n_other, 8) * 8);
-  // (the UNIT kernels address the gathered table with 32-bit byte offsets)
-  const bool unit = sd.unit && t->opt_unit && other == t->factor[1 - pidx].ptr &&
-                    static_cast<uint64_t>(p.zero_row + 8) * t->KP * sizeof(float) < (uint64_t(1) << 32);
-  const bool cg = sc->solver_type == IRS_SOLVER_CG;
+  p.zero_row = static_cast<int32_t>(f.zero_row);
   auto pp_gramian_term = [&]() {
     // the Gramian term of every row's gradient at once: (target @ P)[r] = P x_r (P is symmetric; its
     // KP rows play the items of user_scores_kernel); R K^2 multiply-adds, ~1 % of the half-step
@@ -1378,17 +1141,10 @@ void launch_solve(irs_ials_trainer *t, Side &sd, const float *other, float *targ
     }
     p.px = t->pp_px.ptr - rb * KPl;
   };
-  if (pp_direct) pp_gramian_term();
-  // CG, short rows: the matrix-free kernel takes the tail of the longest-first task list
-  int n_regular = sd.n_tasks;
-  // short rows (<= 32 entries) of a side that has enough of them: Cholesky in its low-rank form /
-  // CG with a diagonal P, both in the eigenbasis of P (ials_eig_kernels.hpp)
-  const bool short_cg_ok = cg && prior == nullptr && sd.n_short > 0 && (t->T <= 4 || t->T == 8) && t->opt_short;
+  if (r.pp_direct) pp_gramian_term();
   hipStream_t short_stream = t->stream;
   auto launch_short_cg = [&]() {  // the matrix-free short-row CG kernels over the tail of the task list
     const int n_regular = sd.n_tasks - sd.n_short;
-    int n_cu = 0;
-    IRS_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, t->device));
     t->prof.begin(pidx == 0 ? "ials_short_cg_user" : "ials_short_cg_item", short_stream);
     IRS_DISPATCH_T8(t->T, {
       constexpr int KPP = 16 * TT;
@@ -1399,211 +1155,144 @@ void launch_solve(irs_ials_trainer *t, Side &sd, const float *other, float *targ
                                     hipFuncAttributeMaxDynamicSharedMemorySize,
                                     static_cast<int>(lds)));
         const int grid = static_cast<int>(
-            std::min<int64_t>(ceil_div(count, SHORT_WAVES * nr), 2 * std::max(n_cu, 1)));
+            std::min<int64_t>(ceil_div(count, SHORT_WAVES * nr), 2 * std::max(t->n_cu, 1)));
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * SHORT_WAVES), lds, short_stream, p,
                            t->P[pidx].ptr, first, count);
       };
-      // the list is longest first: [general | 17..32 entries | <= 16 entries]
-      if (t->opt_short2) {
-        launch(ials_cg_short_kernel<KPP, 32, 1>, n_regular, sd.n_short - sd.n_short16, 1);
-        launch(ials_cg_short_kernel<KPP, 16, 2>, sd.n_tasks - sd.n_short16, sd.n_short16, 2);
-      } else {
-        launch(ials_cg_short_kernel<KPP, 32, 1>, n_regular, sd.n_short - sd.n_short16, 1);
-        launch(ials_cg_short_kernel<KPP, 16, 1>, sd.n_tasks - sd.n_short16, sd.n_short16, 1);
-      }
+      // the list is longest first: [general | 17..32 entries | <= 16 entries (two rows per wave: SHORT2)]
+      launch(ials_cg_short_kernel<KPP, 32, 1>, n_regular, sd.n_short - sd.n_short16, 1);
+      if (t->opt_short2) launch(ials_cg_short_kernel<KPP, 16, 2>, sd.n_tasks - sd.n_short16, sd.n_short16, 2);
+      else launch(ials_cg_short_kernel<KPP, 16, 1>, sd.n_tasks - sd.n_short16, sd.n_short16, 1);
     });
     t->prof.end(short_stream);
   };
-  const bool eig_cand = prior == nullptr && !pp_direct && other == t->factor[1 - pidx].ptr &&
-                        eig_begin(t, sd, pidx, cg);
-  bool short_forked = false;
-  if (eig_cand) {
-    n_regular = sd.n_tasks - sd.n_short;  // (the long rows start now, beside the decomposition)
-  } else if (short_cg_ok) {
+  // (diagnostics: a half-step the eigenbasis path was open to starts from "not taken")
+  if (!prior && !r.pp_direct && f.other_own) t->eig_last = 0;
+  if (r.eig_candidate) {
+    eig_begin(t, pidx);  // (the long rows start now, beside the decomposition)
+  } else if (r.short_cg_ok) {
     // the short-row kernels (latency bound, low issue rate) run BESIDE the kernels of the long rows
     // (matrix-core bound) on the second stream when there are enough of them to matter
-    if (sd.n_short >= 65536) {
-      if (!t->stream2) {
-        IRS_HIP(hipStreamCreateWithFlags(&t->stream2, hipStreamNonBlocking));
-        IRS_HIP(hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming));
-        IRS_HIP(hipEventCreateWithFlags(&t->ev_join, hipEventDisableTiming));
-      }
-      IRS_HIP(hipEventRecord(t->ev_fork, t->stream));
-      IRS_HIP(hipStreamWaitEvent(t->stream2, t->ev_fork, 0));
-      short_stream = t->stream2;
-      short_forked = true;
-    }
+    if (r.short_fork) short_stream = t->fork();
     launch_short_cg();
     short_stream = t->stream;
-    n_regular = sd.n_tasks - sd.n_short;
   }
-  // the kernels of the K x K systems over `count` tasks starting at `tasks_begin`
   // rows cut into many chunks: their partial Gramians are summed in groups first (ials_kernels.hpp)
   auto fold_partials = [&](int partial_floats) {
     if (sd.n_fold <= 0) return;
     t->prof.launch("ials_fold_partials", fold_partials_kernel, dim3(sd.n_fold, ceil_div(partial_floats / 4, 256)),
                    dim3(256), 0, t->stream, t->split_partial.ptr, partial_floats, sd.fold.ptr);
   };
+  // how a family launches a kernel over n_items tasks (or split rows)
+  auto per_wave = [&](SolveKernel kernel, int n_items, const char *name) {
+    t->prof.launch(name, kernel, dim3(ceil_div(n_items, SOLVE_WAVES)), dim3(64 * SOLVE_WAVES), 0, t->stream, p);
+  };
+  auto per_wave8 = [&](SolveKernel kernel, int n_items, const char *name) {
+    t->prof.begin(name, t->stream);
+    hipLaunchKernelGGL(kernel, dim3(n_items), dim3(64), 0, t->stream, p);
+    t->prof.end(t->stream);
+  };
+  auto per_workgroup = [&](size_t lds) {
+    return [&, lds](SolveKernel kernel, int n_items, const char *name) {
+      IRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+      t->prof.begin(name, t->stream);
+      hipLaunchKernelGGL(kernel, dim3(n_items), dim3(256), lds, t->stream, p);
+      t->prof.end(t->stream);
+    };
+  };
+  // the kernels of the K x K systems over `count` tasks starting at `tasks_begin`; with_split: then the
+  // rows cut into chunks, from the partial Gramians their chunks left (without: the short rows after the
+  // eigenbasis path declined)
   auto launch_dense = [&](const Task *tasks_begin, int count, bool with_split) {
-  const int n_regular = count;
-  p.tasks = tasks_begin;
-  p.n_tasks = count;
-  if (!cg && (t->T >= 12 || (t->T == 8 && !t->opt_wave128)) && t->opt_wg16) {
-    // 128 < K <= 256, Cholesky: one workgroup per row, 16-row block steps on the matrix cores
-    // (ials_wg16_kernels.hpp).  K <= 128 stays on the one-wave-per-row kernel, whose solve is the
-    // same block algorithm in one wave (ials_chol16.hpp): ML-20M shape, K = 128: 8.7 ms against
-    // 12.5 ms per epoch, because four waves per row repeat the gather's vector work four times.
-    IRS_DISPATCH_TW(t->T, {
-      using G = Geo<TT>;
-      constexpr size_t lds = WgChol<TT>::LDS_FLOATS * sizeof(float);
-      t->split_partial.alloc(static_cast<size_t>(std::max(sd.n_slots, 1)) * G::PARTIAL_FLOATS);
+    p.tasks = tasks_begin;
+    p.n_tasks = count;
+    const bool x3 = with_split ? r.x3 : r.x3_declined;
+    auto run = [&](int partial_floats, auto &&launch, SolveKernel tasks_kernel, SolveKernel split_kernel) {
+      t->split_partial.alloc(static_cast<size_t>(std::max(sd.n_slots, 1)) * partial_floats);
       p.partials = t->split_partial.ptr;
-      auto launch = [&](auto kernel, int n_items, const char *name) {
-        if (n_items <= 0) return;
-        IRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    static_cast<int>(lds)));
-        t->prof.begin(name, t->stream);
-        hipLaunchKernelGGL(kernel, dim3(n_items), dim3(256), lds, t->stream, p);
-        t->prof.end(t->stream);
-      };
-      launch(ials_wg16_cholesky_kernel<TT, 0>, n_regular, kNames[0][0][pidx]);
-      if (with_split) fold_partials(G::PARTIAL_FLOATS);
-      if (with_split) launch(ials_wg16_cholesky_kernel<TT, 1>, sd.n_split, kNames[0][1][pidx]);
-    });
-  } else if (t->T == 8 && t->opt_wave128) {
-    // 64 < K <= 128: the 36 tiles still fit one wave's 512 registers (144 of them
-    // accumulators), so the one-wave-per-task kernel is reused with the MFMA panel Cholesky /
-    // a two-rows-per-lane CG (46 KB LDS per wave for the spilled tiles: three waves per CU)
-    using G = Geo<8>;
-    t->split_partial.alloc(static_cast<size_t>(std::max(sd.n_slots, 1)) * G::PARTIAL_FLOATS);
-    p.partials = t->split_partial.ptr;
-    if (n_regular > 0) {
-      t->prof.begin(kNames[cg][0][pidx], t->stream);
-      // (unit confidences: the bf16x3 rank update of ials_kernels.hpp, round 6 also at T = 8 - 216 bf16 matrix
-      // instructions of 16 cycles per 32 entries instead of 288 fp32-input ones of 32)
-      // The bf16x3 kernels hold ~410-440 registers (one wave per SIMD, like the CG kernels always did); the
-      // fp32-input Cholesky kernel holds 236 (two).  Under Cholesky the second wave is worth more than the
-      // faster rank update when rows are short - ML-20M user half, 144 entries per task: 4.8 ms fp32-input,
-      // 5.3 ms bf16x3; item half, 544 per task: 3.1 -> 2.5 ms - so the choice goes by the mean task length.
-      // (`unit` also requires a gathered table below 4 GB - the fp32-input UNIT kernels address it with
-      // 32-bit byte offsets; the T = 8 bf16x3 gather uses 64-bit row addresses and has no such limit)
-      const bool x3_any = sd.unit && t->opt_unit && other == t->factor[1 - pidx].ptr && t->opt_bf16x3;
-      const bool x3 = x3_any && (cg || sd.long_entries >= int64_t(320) * std::max(n_regular, 1));
-      if (cg && x3)
-        hipLaunchKernelGGL((ials_solve_kernel<8, 1, 0, true, true>), dim3(n_regular), dim3(64), 0, t->stream, p);
-      else if (cg && unit)
-        hipLaunchKernelGGL((ials_solve_kernel<8, 1, 0, true>), dim3(n_regular), dim3(64), 0, t->stream, p);
-      else if (cg)
-        hipLaunchKernelGGL((ials_solve_kernel<8, 1, 0>), dim3(n_regular), dim3(64), 0, t->stream, p);
-      else if (x3)
-        hipLaunchKernelGGL((ials_solve_kernel<8, 0, 0, true, true>), dim3(n_regular), dim3(64), 0, t->stream, p);
-      else if (unit)
-        hipLaunchKernelGGL((ials_solve_kernel<8, 0, 0, true>), dim3(n_regular), dim3(64), 0, t->stream, p);
-      else
-        hipLaunchKernelGGL((ials_solve_kernel<8, 0, 0>), dim3(n_regular), dim3(64), 0, t->stream, p);
-      t->prof.end(t->stream);
-    }
-    if (with_split && sd.n_split > 0) {
-      fold_partials(G::PARTIAL_FLOATS);
-      t->prof.begin(kNames[cg][1][pidx], t->stream);
-      if (cg && sd.unit && t->opt_unit && other == t->factor[1 - pidx].ptr && t->opt_bf16x3)  // (lower-form partials)
-        hipLaunchKernelGGL((ials_solve_kernel<8, 1, 1, false, true>), dim3(sd.n_split), dim3(64), 0, t->stream, p);
-      else if (cg)
-        hipLaunchKernelGGL((ials_solve_kernel<8, 1, 1>), dim3(sd.n_split), dim3(64), 0, t->stream, p);
-      else
-        hipLaunchKernelGGL((ials_solve_kernel<8, 0, 1>), dim3(sd.n_split), dim3(64), 0, t->stream, p);
-      t->prof.end(t->stream);
-    }
-  } else if (t->T <= 4) {
-    IRS_DISPATCH_T(t->T, {
-      using G = Geo<TT>;
-      t->split_partial.alloc(static_cast<size_t>(std::max(sd.n_slots, 1)) * G::PARTIAL_FLOATS);
-      p.partials = t->split_partial.ptr;
-      if (n_regular > 0) {
-        const dim3 grid(ceil_div(n_regular, SOLVE_WAVES)), block(64 * SOLVE_WAVES);
-        const char *name = kNames[cg][0][pidx];
-        if (pp_direct && unit && t->opt_bf16x3 && TT == 4)  // (the gradient form on the bf16x3 rank update, round 6)
-          t->prof.launch(name, ials_solve_kernel<4, 0, 0, true, true, true>, grid, block, 0, t->stream, p);
-        else if (pp_direct && unit)
-          t->prof.launch(name, ials_solve_kernel<TT, 0, 0, true, false, true>, grid, block, 0, t->stream, p);
-        else if (pp_direct)
-          t->prof.launch(name, ials_solve_kernel<TT, 0, 0, false, false, true>, grid, block, 0, t->stream, p);
-        else if (cg && unit && t->opt_bf16x3 && TT == 4)
-          t->prof.launch(name, ials_solve_kernel<4, 1, 0, true, true>, grid, block, 0, t->stream, p);
-        else if (cg && unit)
-          t->prof.launch(name, ials_solve_kernel<TT, 1, 0, true>, grid, block, 0, t->stream, p);
-        else if (cg)
-          t->prof.launch(name, ials_solve_kernel<TT, 1, 0>, grid, block, 0, t->stream, p);
-        else if (unit && t->opt_bf16x3 && TT == 4)
-          t->prof.launch(name, ials_solve_kernel<4, 0, 0, true, true>, grid, block, 0, t->stream, p);
-        else if (unit)
-          t->prof.launch(name, ials_solve_kernel<TT, 0, 0, true>, grid, block, 0, t->stream, p);
-        else
-          t->prof.launch(name, ials_solve_kernel<TT, 0, 0>, grid, block, 0, t->stream, p);
-      }
+      if (count > 0) launch(tasks_kernel, count, kNames[r.cg][0][pidx]);
       if (with_split && sd.n_split > 0) {
-        fold_partials(G::PARTIAL_FLOATS);
-        const dim3 grid(ceil_div(sd.n_split, SOLVE_WAVES)), block(64 * SOLVE_WAVES);
-        if (pp_direct)
-          t->prof.launch(kNames[cg][1][pidx], ials_solve_kernel<TT, 0, 1, false, false, true>, grid, block, 0,
-                         t->stream, p);
-        else if (cg && unit && t->opt_bf16x3 && TT == 4)  // (the bf16x3 chunks left lower-form partials)
-          t->prof.launch(kNames[cg][1][pidx], ials_solve_kernel<4, 1, 1, false, true>, grid, block, 0, t->stream, p);
-        else if (cg)
-          t->prof.launch(kNames[cg][1][pidx], ials_solve_kernel<TT, 1, 1>, grid, block, 0, t->stream, p);
-        else
-          t->prof.launch(kNames[cg][1][pidx], ials_solve_kernel<TT, 0, 1>, grid, block, 0, t->stream, p);
+        fold_partials(partial_floats);
+        launch(split_kernel, sd.n_split, kNames[r.cg][1][pidx]);
       }
-    });
-  } else {
-    IRS_DISPATCH_TW(t->T, {
-      using G = Geo<TT>;
-      constexpr size_t lds = WgGeo<TT>::LDS_FLOATS * sizeof(float);
-      t->split_partial.alloc(static_cast<size_t>(std::max(sd.n_slots, 1)) * G::PARTIAL_FLOATS);
-      p.partials = t->split_partial.ptr;
-      auto launch = [&](auto kernel, int n_items, const char *name) {
-        IRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    static_cast<int>(lds)));
-        t->prof.begin(name, t->stream);
-        hipLaunchKernelGGL(kernel, dim3(n_items), dim3(256), lds, t->stream, p);
-        t->prof.end(t->stream);
-      };
-      if (n_regular > 0) {
-        if (cg)
-          launch(ials_wg_solve_kernel<TT, 1, 0>, n_regular, kNames[1][0][pidx]);
-        else
-          launch(ials_wg_solve_kernel<TT, 0, 0>, n_regular, kNames[0][0][pidx]);
-      }
-      if (with_split && sd.n_split > 0) {
-        fold_partials(G::PARTIAL_FLOATS);
-        if (cg)
-          launch(ials_wg_solve_kernel<TT, 1, 1>, sd.n_split, kNames[1][1][pidx]);
-        else
-          launch(ials_wg_solve_kernel<TT, 0, 1>, sd.n_split, kNames[0][1][pidx]);
-      }
-    });
-  }
-  IRS_HIP(hipGetLastError());
-  };  // launch_dense
-  launch_dense(sd.tasks.ptr, n_regular, true);
-  if (pp_direct) {  // the further sweeps of hpp:516-530, each a step from where the last one ended
+    };
+    // The instance of a family, selected explicitly: the set of ials_solve_kernel<T, SOLVER, MODE, UNIT, BF16X3,
+    // RESID> is closed (SOLVER 0 Cholesky / 1 CG; MODE 0: the tasks, 1: the rows cut into chunks, from their
+    // partials).  bf16x3 exists at T = 4 and 8 only, the gradient form (RESID: pp_direct) at T <= 4 and Cholesky
+    // only, and a MODE 1 kernel reads no entries, so it has no UNIT form - its BF16X3 form (CG only) takes the
+    // lower-form partials the bf16x3 chunks leave.
+    SolveKernel k = nullptr, ks = nullptr;  // of the tasks, of the split rows
+    switch (r.family) {
+      case DenseFamily::WG16:
+        // 128 < K <= 256, Cholesky: one workgroup per row, 16-row block steps on the matrix cores
+        // (ials_wg16_kernels.hpp).  K <= 128 stays on the one-wave-per-row kernel, whose solve is the
+        // same block algorithm in one wave (ials_chol16.hpp): ML-20M shape, K = 128: 8.7 ms against
+        // 12.5 ms per epoch, because four waves per row repeat the gather's vector work four times.
+        IRS_DISPATCH_TW(t->T, run(Geo<TT>::PARTIAL_FLOATS, per_workgroup(WgChol<TT>::LDS_FLOATS * sizeof(float)),
+                                  ials_wg16_cholesky_kernel<TT, 0>, ials_wg16_cholesky_kernel<TT, 1>));
+        break;
+      case DenseFamily::WAVE8:
+        // 64 < K <= 128: the 36 tiles still fit one wave's 512 registers (144 of them
+        // accumulators), so the one-wave-per-task kernel is reused with the MFMA panel Cholesky /
+        // a two-rows-per-lane CG (46 KB LDS per wave for the spilled tiles: three waves per CU)
+        // (unit confidences: the bf16x3 rank update of ials_kernels.hpp, round 6 also at T = 8 - 216 bf16 matrix
+        // instructions of 16 cycles per 32 entries instead of 288 fp32-input ones of 32)
+        if (r.cg && x3) k = ials_solve_kernel<8, 1, 0, true, true>;
+        else if (r.cg && r.unit) k = ials_solve_kernel<8, 1, 0, true>;
+        else if (r.cg) k = ials_solve_kernel<8, 1, 0>;
+        else if (x3) k = ials_solve_kernel<8, 0, 0, true, true>;
+        else if (r.unit) k = ials_solve_kernel<8, 0, 0, true>;
+        else k = ials_solve_kernel<8, 0, 0>;
+        if (r.x3_split) ks = ials_solve_kernel<8, 1, 1, false, true>;
+        else if (r.cg) ks = ials_solve_kernel<8, 1, 1>;
+        else ks = ials_solve_kernel<8, 0, 1>;
+        run(Geo<8>::PARTIAL_FLOATS, per_wave8, k, ks);
+        break;
+      case DenseFamily::WAVE:
+        IRS_DISPATCH_T(t->T, {
+          if (r.pp_direct && x3) k = ials_solve_kernel<4, 0, 0, true, true, true>;  // (x3: T = 4, SolveRoute)
+          else if (r.pp_direct && r.unit) k = ials_solve_kernel<TT, 0, 0, true, false, true>;
+          else if (r.pp_direct) k = ials_solve_kernel<TT, 0, 0, false, false, true>;
+          else if (r.cg && x3) k = ials_solve_kernel<4, 1, 0, true, true>;
+          else if (r.cg && r.unit) k = ials_solve_kernel<TT, 1, 0, true>;
+          else if (r.cg) k = ials_solve_kernel<TT, 1, 0>;
+          else if (x3) k = ials_solve_kernel<4, 0, 0, true, true>;
+          else if (r.unit) k = ials_solve_kernel<TT, 0, 0, true>;
+          else k = ials_solve_kernel<TT, 0, 0>;
+          if (r.pp_direct) ks = ials_solve_kernel<TT, 0, 1, false, false, true>;
+          else if (r.x3_split) ks = ials_solve_kernel<4, 1, 1, false, true>;
+          else if (r.cg) ks = ials_solve_kernel<TT, 1, 1>;
+          else ks = ials_solve_kernel<TT, 0, 1>;
+          run(Geo<TT>::PARTIAL_FLOATS, per_wave, k, ks);
+        });
+        break;
+      case DenseFamily::WG:
+        IRS_DISPATCH_TW(t->T, {
+          if (r.cg) k = ials_wg_solve_kernel<TT, 1, 0>;
+          else k = ials_wg_solve_kernel<TT, 0, 0>;
+          if (r.cg) ks = ials_wg_solve_kernel<TT, 1, 1>;
+          else ks = ials_wg_solve_kernel<TT, 0, 1>;
+          run(Geo<TT>::PARTIAL_FLOATS, per_workgroup(WgGeo<TT>::LDS_FLOATS * sizeof(float)), k, ks);
+        });
+        break;
+    }
+    IRS_HIP(hipGetLastError());
+  };
+  launch_dense(sd.tasks.ptr, r.n_regular, true);
+  if (r.pp_direct) {  // the further sweeps of hpp:516-530, each a step from where the last one ended
     for (uint64_t it = 1; it < sc->ialspp_iteration; it++) {
       pp_gramian_term();
-      launch_dense(sd.tasks.ptr, n_regular, true);
+      launch_dense(sd.tasks.ptr, r.n_regular, true);
     }
   }
-  if (short_forked) {
-    IRS_HIP(hipEventRecord(t->ev_join, t->stream2));
-    IRS_HIP(hipStreamWaitEvent(t->stream, t->ev_join, 0));
-  }
-  if (eig_cand && !eig_finish(t, sd, other, target, pidx, cg, p.max_cg_steps, p.err_flag)) {
+  if (r.short_fork) t->join();
+  if (r.eig_candidate && !eig_finish(t, sd, other, target, pidx, r.cg, p.max_cg_steps, p.err_flag)) {
     // the eigenbasis path declined (ill-conditioned P + reg I): the short rows through the usual kernels
     p.tasks = sd.tasks.ptr;
     p.n_tasks = sd.n_tasks;
-    if (short_cg_ok) launch_short_cg();
-    else launch_dense(sd.tasks.ptr + n_regular, sd.n_short, false);
+    if (r.short_cg_ok) launch_short_cg();
+    else launch_dense(sd.tasks.ptr + r.n_regular, sd.n_short, false);
   }
 }
 
@@ -1914,18 +1603,8 @@ irs_status irs_ials_destroy(irs_ials_trainer *t) {
     if (t) {
       (void)hipSetDevice(t->device);
       t->prof.clear();
-      if (t->stream2) {
-        (void)hipStreamSynchronize(t->stream2);
-        (void)hipStreamDestroy(t->stream2);
-        (void)hipEventDestroy(t->ev_fork);
-        (void)hipEventDestroy(t->ev_join);
-      }
-      if (t->stream3) {
-        (void)hipStreamSynchronize(t->stream3);
-        (void)hipStreamDestroy(t->stream3);
-        (void)hipEventDestroy(t->ev_fork3);
-        (void)hipEventDestroy(t->ev_join3);
-      }
+      t->beside.destroy();
+      t->beside3.destroy();
       if (t->eig_resident) (void)hipHostFree(t->eig_resident);
       delete t;
     }
@@ -2680,7 +2359,7 @@ irs_status irs_ials_compute_loss(irs_ials_trainer *t, const irs_ials_solver_conf
       for (size_t i = 0; i < pu.size(); i++) s += static_cast<double>(pu[i]) * pi[i];
       loss = s / t->cfg.alpha0;
     }
-    const float bias = t->cfg.loss_type == IRS_LOSS_IALSPP ? 0.0f : t->cfg.alpha0;
+    const float bias = t->bias();
     t->row_loss.alloc(static_cast<size_t>(std::max(t->n_users, t->n_items)));
     double h[2] = {0.0, 0.0};
     for (int s = 0; s < 2; s++) {

@@ -26,6 +26,8 @@
 #include <cstdint>
 #include <utility>
 
+#include "ials_types.hpp"
+
 namespace irs {
 namespace ials {
 
@@ -42,31 +44,7 @@ constexpr int SOLVE_WAVES = 1;  // waves per solve workgroup: waves never cooper
 #define SOLVE_MIN_WAVES_PER_SIMD_K64 SOLVE_MIN_WAVES_PER_SIMD  // the same for the K <= 64 kernels (A/B builds)
 #endif
 
-struct Task {
-  int32_t row;    // row of the solved side
-  int32_t begin;  // [begin, end) into indices / data
-  int32_t end;
-  int32_t slot;   // < 0: whole row, solve inline; >= 0: partial Gramian slot
-};
-
-struct SplitRow {
-  int32_t row;
-  int32_t first_slot;
-  int32_t n_slots;      // slots the second kernel adds: first_slot + i * slot_stride
-  int32_t nnz;
-  int32_t slot_stride;  // 1, or FOLD_GROUP once fold_partials_kernel has summed each group into its first slot
-};
-
-// A row cut into more than FOLD_MIN chunks has its partial Gramians summed in groups of
-// FOLD_GROUP first (one thread per float4 of the partial, every group in parallel), so that the
-// one wave (or workgroup) that finishes the row adds at most FOLD_MIN partials one after another.
-constexpr int FOLD_GROUP = 16;
-constexpr int FOLD_MIN = 32;
-struct FoldGroup {
-  int32_t first_slot;
-  int32_t count;
-};
-
+// (Task, SplitRow, FoldGroup: ials_types.hpp)
 __global__ __launch_bounds__(256) void fold_partials_kernel(float *__restrict__ partials, int partial_floats,
                                                             const FoldGroup *__restrict__ groups) {
   const FoldGroup g = groups[blockIdx.x];

@@ -35,32 +35,10 @@
 namespace irs {
 namespace ials {
 
-#ifndef IRS_MF_J
-#define IRS_MF_J 10
-#endif
 #ifndef IRS_MF_PUNROLL
 #define IRS_MF_PUNROLL 2
 #endif
-constexpr int MF_J = IRS_MF_J;           // groups of four gathered rows a wave keeps in registers
-constexpr int MF_NCAP = 32 * MF_J;       // longest resident row: 8 waves x MF_J groups of 4 entries
-// row classes by stored entries, longest first: class 0 = level-synchronous, then the resident
-// classes of mf_cg_rows_kernel<KP, R, W, 10> (capacity 40 W): <1, 8>, <1, 4>, <2, 2>, <4, 1>
-constexpr int MF_CHUNK = 1024;  // entries per chunk of a level-synchronous row
-constexpr int MF_CLASSES = 5;
-constexpr int32_t MF_CAPS[MF_CLASSES] = {INT32_MAX, MF_NCAP, 16 * MF_J, 8 * MF_J, 4 * MF_J};
-
-struct MfLongRow {
-  int32_t row;          // row of the solved side
-  int32_t first_chunk;  // chunks [first_chunk, first_chunk + n_chunks) in row order
-  int32_t n_chunks;
-  int32_t pad;
-};
-struct MfChunk {
-  int32_t lrow;   // index into the long-row list
-  int32_t begin;  // [begin, end) into indices / data
-  int32_t end;
-  int32_t pad;
-};
+// (MF_J, MF_NCAP, MF_CHUNK, the row classes MF_CAPS, MfLongRow, MfChunk: ials_types.hpp)
 
 struct MfParams {
   const int32_t *rows;  // resident kernels: row = rows[row_first + blockIdx.x] (longest first)

@@ -13,7 +13,7 @@
 namespace irs {
 namespace ials {
 
-constexpr int SHORT_MAX = 32;    // rows up to this many stored entries take a short kernel
+// (SHORT_MAX, the longest row that takes a short kernel: ials_types.hpp)
 constexpr int SHORT_WAVES = 8;   // waves per workgroup (they share P in LDS)
 
 template <int KP> struct ShortGeo {

@@ -9,6 +9,9 @@ available on the pool; this covers the code that runs on host threads:
 - tests/host/knn_host_prep_main.cpp: the rest of knn_host_prep.hpp, i.e. what a kNN compute call does on the host
   before it launches - entry scan, chunk cuts, the threaded target pass, launch order, variant choice, arena layout.
 - tests/host/eval_host_prep_main.cpp: eval_host_prep.hpp.
+- tests/host/ials_host_plan_main.cpp: ials_host_plan.hpp, i.e. what the iALS path decides on the host - the task plan
+  of a side (chunks, fold groups, the short tail, the row classes) and the route of a half-step (kernel family and
+  instance flags, against the former chains of conditions).
 The stream, event and buffer handling of knn.hip itself needs a device and is not compiled here."""
 import os
 import shutil
@@ -141,3 +144,44 @@ def test_knn_host_preparation_under_thread_sanitizer(tmp_path):
     assert r.returncode == 0, r.stderr[-4000:]
     assert "WARNING: ThreadSanitizer" not in r.stderr, r.stderr[-4000:]
     assert "knn_host_prep ok" in r.stdout
+
+
+def _ials_host_plan(tmp_path, flags, env_extra):
+    exe = str(tmp_path / "ials_host_plan_main")
+    src = os.path.join(ROOT, "tests", "host", "ials_host_plan_main.cpp")
+    subprocess.check_call([_HOST_CXX, "-std=c++17", "-O1", "-g", "-pthread", "-ffp-contract=off", *flags,
+                           "-fno-omit-frame-pointer", src, "-o", exe])
+    return subprocess.run([exe], env=dict(os.environ, **env_extra), capture_output=True, text=True, timeout=600)
+
+
+@pytest.mark.skipif(_HOST_CXX is None, reason="needs a host C++ compiler")
+def test_ials_host_plan_under_address_and_ub_sanitizers(tmp_path):
+    """irspack_amd/csrc/ials_host_plan.hpp - the task plan at the sizes where the chunk rule changes (exact lists for
+    hand-made row pointers; tiling, dense slots, fold groups, the short tail that stops at a split row's chunk), the
+    regulariser on several threads, the route of a half-step and the iALS++ variant over every switch setting against
+    the former chains of conditions - in a program of its own (tests/host/ials_host_plan_main.cpp), every report fatal."""
+    r = _ials_host_plan(tmp_path, ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], {})
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+    assert "ials_host_plan ok" in r.stdout
+
+
+@pytest.mark.skipif(_HOST_CXX is None, reason="needs a host C++ compiler")
+def test_ials_host_plan_under_thread_sanitizer(tmp_path):
+    """The same program under ThreadSanitizer: the regulariser pass on several threads, and the route enumeration
+    on eight (there with every 29th switch setting: every access is instrumented)."""
+    r = _ials_host_plan(tmp_path, ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1 second_deadlock_stack=1"})
+    if "unexpected memory mapping" in r.stderr or "personality" in r.stderr:
+        pytest.skip("ThreadSanitizer cannot map its shadow memory in this container: " + r.stderr[:200])
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert "WARNING: ThreadSanitizer" not in r.stderr, r.stderr[-4000:]
+    assert "ials_host_plan ok" in r.stdout
+
+
+@pytest.mark.skipif(_HOST_CXX is None, reason="needs a host C++ compiler")
+def test_ials_host_plan_plain_optimised_build(tmp_path):
+    """The same program without a sanitizer at -O3 (with the library's -ffp-contract=off): the build whose float
+    arithmetic is the library's."""
+    r = _ials_host_plan(tmp_path, ["-O3"], {})
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert "ials_host_plan ok" in r.stdout
