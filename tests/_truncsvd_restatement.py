@@ -37,6 +37,34 @@ def randomized_truncated_svd(X, n_components, random_seed=0, dtype=np.float64, n
     return np.asarray(z), s, Vt
 
 
+def range_gram(A, omega, n_iter, dtype=np.float64):
+    """What ``irs_truncsvd_range(omega, l, n_iter)`` hands back, restated in ``dtype``: the device's own power
+    iteration, not sklearn's.  ``Q = omega``; ``n_iter`` times ``Y = A Q``, normalise, ``Q = A^T Y``, normalise;
+    then ``Y = A Q`` and ``G = Y^T Y``.  Normalise a block ``B`` of ``l`` columns: ``G = B^T B + d I`` with
+    ``d = 1e-5 * trace(B^T B) / l``, its Cholesky factor ``L`` (unique, so the result can be compared element by
+    element), ``W = L^-1`` and ``B <- B W^T``."""
+    A = sps.csr_matrix(A, dtype=dtype)
+    At = A.T.tocsr()
+    Q = np.ascontiguousarray(omega, dtype=dtype)
+    l = Q.shape[1]
+    eye = np.eye(l, dtype=dtype)
+
+    def normalise(B):
+        G = B.T @ B
+        d = dtype(1e-5) * np.trace(G) / dtype(l)
+        L = np.linalg.cholesky(G + d * eye)
+        W = scipy.linalg.solve_triangular(L, eye, lower=True, check_finite=False)
+        return B @ W.T
+
+    for _ in range(n_iter):
+        Q = normalise(np.asarray(A @ Q))
+        Q = normalise(np.asarray(At @ Q))
+    Y = np.asarray(A @ Q)
+    G = Y.T @ Y
+    assert G.dtype == dtype
+    return G
+
+
 def score_error(z, components, z64, components64):
     """max abs difference of the score matrices ``z @ components`` and the largest magnitude of the float64 one"""
     S = np.asarray(z, dtype=np.float64) @ np.asarray(components, dtype=np.float64)
