@@ -13,6 +13,8 @@
 #include <cstdint>
 #include <limits>
 
+#include "eval_host_prep.hpp"  // FZ_MAX_CUTOFF, EM_*, SF_ITEMS, SF_USERS
+
 namespace irs {
 namespace eval {
 
@@ -23,7 +25,6 @@ typedef float fz_f32x4 __attribute__((ext_vector_type(4)));
 // would drain the operand loads that are in flight for the next tile.
 #define FZ_LDS_FENCE() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 
-constexpr int FZ_MAX_CUTOFF = 32;  // largest cutoff of the fused paths
 constexpr int FZ_SROW = 68;        // LDS row stride of the score tile (floats)
 
 // mask CSR rows -> bitmap rows (the bitmap is zeroed by the host first), one wave per row
@@ -75,12 +76,6 @@ __global__ __launch_bounds__(256) void mask_count_kernel(const uint64_t *__restr
 // candidate list abandon the path (flag) and the host runs the two-pass one.
 namespace irs {
 namespace eval {
-
-constexpr int EM_CAP = 1024;     // candidate slots per user
-constexpr int EM_SAMPLE = 2048;  // items of the sample pass (items in catalogue order)
-constexpr int EM_SAMPLE_SORTED = 512;  // ... when the items are sorted by norm (bounded variant)
-constexpr int EM_SAMPLE2 = 4096;       // second-chance sample of the rows the first left hard
-constexpr int EM_HARD_CAP = 2048;      // rows the second chance handles
 
 struct EmitParams {
   const float *user, *item;
@@ -201,7 +196,7 @@ struct SampleParams {
   int32_t *hard;            // [rows]
   int32_t *bad_flag;        // bit 0: non-finite score
 };
-constexpr int SF_ITEMS = 512, SF_USERS = 16, SF_SROW = 516;  // (516: rows 4 apart land 16 banks apart)
+constexpr int SF_SROW = 516;  // LDS row stride (516: rows 4 apart land 16 banks apart)
 constexpr size_t SF_LDS_BYTES = 2 * SF_USERS * SF_SROW * sizeof(float) + 8 * 2 * SF_ITEMS;
 
 __device__ __forceinline__ uint32_t sf_key(float v) {  // order-preserving: a < b <=> key(a) < key(b)

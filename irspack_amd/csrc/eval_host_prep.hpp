@@ -18,6 +18,19 @@ namespace eval {
 // running totals (evaluator.cpp:76-85) - so its float64 sums are the default loop's to the last bit.
 constexpr int64_t HOST_LOOP_ROWS = 128;
 
+// Sizes that both the kernels and the host rules (eval_emit_plan.hpp) are written against: defined here once, the
+// kernel headers take them from this file.
+constexpr int SEL_CAP = 2048;    // largest cutoff ranked in LDS (16 KB keys + 8 KB indices)
+constexpr int RANK_MAXQ = 32;    // rank_rows_kernel MODE 2: key slots per lane held in registers
+constexpr int64_t HIST_DIRECT_MAX = 36864;  // largest catalogue whose item counters fit one CU's LDS
+constexpr int FZ_MAX_CUTOFF = 32;  // largest cutoff of the fused paths
+constexpr int EM_CAP = 1024;     // candidate slots per user
+constexpr int EM_SAMPLE = 2048;  // items of the sample pass (items in catalogue order)
+constexpr int EM_SAMPLE_SORTED = 512;  // ... when the items are sorted by norm (bounded variant)
+constexpr int EM_SAMPLE2 = 4096;       // second-chance sample of the rows the first left hard
+constexpr int EM_HARD_CAP = 2048;      // rows the second chance handles
+constexpr int SF_ITEMS = 512, SF_USERS = 16;  // sample_tau_fused_kernel: items of its sample, users per tile
+
 // EvalParams::rec_mode of a call with `n_lists` candidate lists: 0 all items, 1 one list, 2 a list per row
 inline int rec_mode_of(int64_t n_lists) { return n_lists == 0 ? 0 : (n_lists == 1 ? 1 : 2); }
 

@@ -26,1132 +26,17 @@
 
 #include "common.hpp"
 #include "eval_host_prep.hpp"
+#include "eval_emit_plan.hpp"
 
-namespace irs {
-namespace eval {
-
-constexpr int SEL_CAP = 2048;  // largest cutoff ranked in LDS (16 KB keys + 8 KB indices)
-
-struct RowOut {
-  double hit, recall, ndcg, precision, map;
-  int32_t valid;   // 1 when the user has ground truth
-  int32_t n_rec;
-};
-
-// order-preserving integer keys; larger key = better score.  NaN ranks last,
-// -0.0 == +0.0 (the reference compares floats, where they tie).
-__device__ __forceinline__ uint64_t order_key(float s) {
-  if (s != s) return 0ull;
-  if (s == 0.f) s = 0.f;
-  uint32_t u = __float_as_uint(s);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return static_cast<uint64_t>(u);
-}
-__device__ __forceinline__ uint64_t order_key(double s) {
-  if (s != s) return 0ull;
-  if (s == 0.0) s = 0.0;
-  uint64_t u = static_cast<uint64_t>(__double_as_longlong(s));
-  return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-}
-template <class T> struct KeyBits;
-template <> struct KeyBits<float> { static constexpr int value = 32; };
-template <> struct KeyBits<double> { static constexpr int value = 64; };
-template <class T> __device__ __forceinline__ bool is_neg_inf(T s) {
-  return s == -std::numeric_limits<T>::infinity();
-}
-
-struct EvalParams {
-  const void *scores;        // [rows, n_items] row-major
-  int64_t rows, n_items;
-  int64_t offset;            // ground-truth row of scores row 0
-  const int32_t *gt_ptr;     // filtered ground truth CSR (relevant ∩ recommendable)
-  const int32_t *gt_idx;
-  int32_t rec_mode;          // 0 all items, 1 global list, 2 per-user lists
-  const int64_t *rec_ptr;
-  const int32_t *rec_items;
-  int32_t cutoff;
-  int32_t retrieve;          // 1: only the ranked lists are wanted (no ground truth, no metrics)
-  int32_t recall_with_cutoff;
-  const double *disc;        // 1 / log2(2 + i)
-  const double *idcg_prefix; // sequential prefix sums of disc
-  RowOut *out;
-  int32_t *rec_out;          // [rows, cutoff] recommended items (-1 padded)
-  unsigned long long *item_cnt;
-  int32_t *todo;             // per row: 1 = left to rank_rows_kernel by rank_wave_kernel (or null)
-  // score row r stands for row row_map[r] of the call (ground truth, outputs); null: r itself
-  const int32_t *row_map = nullptr;
-  // cutoff > SEL_CAP (rank_rows_kernel<..., BIG>): the selected (key, index, hit) lists live in
-  // global scratch, `big_cap` (a power of two >= cutoff) entries per workgroup of the launch;
-  // the launch covers the rows row_base + blockIdx.x
-  int64_t row_base = 0;
-  uint64_t *big_key = nullptr;
-  int32_t *big_idx = nullptr;
-  uint8_t *big_hit = nullptr;
-  int32_t big_cap = 0;
-};
-
-// key value no score maps to (it is the image of a negative NaN pattern, and NaNs are
-// canonicalised to 0): marks "not rankable" (-inf) in the cached keys
-constexpr uint64_t KEY_SKIP = 1ull;
-template <class T> struct KeyStore;
-template <> struct KeyStore<float> { using type = uint32_t; };
-template <> struct KeyStore<double> { using type = uint64_t; };
-
-// NT threads per user row.  Wave w owns the contiguous candidates [w * span, (w + 1) * span) in
-// 64-wide steps: slot q of lane l is candidate w * span + 64 q + l, so (wave, slot, lane)
-// order is index order.  Where the keys live between the passes:
-//   MODE 2 (NT = 1024, float scores, <= 32 slots per lane): in registers - one pass over the
-//          scores in HBM, no LDS traffic for keys (same speed as MODE 1 today: the kernel is
-//          bound by its barrier / latency chain, and the 64-VGPR budget that a second
-//          workgroup per CU would need spills);
-//   MODE 1 (NT = 1024): in dynamic LDS - one pass over the scores, one workgroup per CU;
-//   MODE 0 (NT = 256): nowhere, every pass re-reads the scores.
-constexpr int RANK_MAXQ = 32;
-
-// BIG (cutoff > SEL_CAP, any cutoff up to n_items like the reference, evaluator.cpp:263-268):
-// the selected lists are kept in global scratch instead of LDS (a workgroup's own global stores
-// are visible to its other waves after __syncthreads: they share the CU's L1), everything else
-// is the same code.
-// POS (the serving calls, retrieve = 1 with candidate lists): the selected entries carry the candidate's POSITION in
-// its list instead of its item, so equal scores come out in candidate order whatever the order of the list
-// (util.hpp:426-504 through a stable sort); the item is looked up when the list is written.  The evaluator's lists
-// are sorted and without duplicates, where the two orders are the same.
-template <class T, int NT, int MODE, int MAXQ = RANK_MAXQ, bool BIG = false, bool POS = false>
-__global__ __launch_bounds__(NT, MODE == 2 ? 4 : 1) void rank_rows_kernel(EvalParams p) {
-  using KeyT = typename KeyStore<T>::type;
-  constexpr int NWV = NT / 64;
-  constexpr bool CACHED = MODE == 1;
-  extern __shared__ __attribute__((aligned(16))) unsigned char rank_dyn[];
-  KeyT *keys = reinterpret_cast<KeyT *>(rank_dyn);
-  __shared__ uint32_t hist[256];
-  __shared__ uint64_t sel_key_lds[BIG ? 1 : SEL_CAP];
-  __shared__ int32_t sel_idx_lds[BIG ? 1 : SEL_CAP];
-  __shared__ uint8_t sel_hit_lds[BIG ? 1 : SEL_CAP];
-  __shared__ int32_t scan_buf[NWV > 4 ? NWV : 4];
-  __shared__ uint64_t sh_prefix;
-  __shared__ int32_t sh_need, sh_count;
-  const int sel_cap = BIG ? p.big_cap : SEL_CAP;
-  uint64_t *sel_key = BIG ? p.big_key + static_cast<size_t>(blockIdx.x) * p.big_cap : sel_key_lds;
-  int32_t *sel_idx = BIG ? p.big_idx + static_cast<size_t>(blockIdx.x) * p.big_cap : sel_idx_lds;
-  uint8_t *sel_hit = BIG ? p.big_hit + static_cast<size_t>(blockIdx.x) * p.big_cap : sel_hit_lds;
-
-  const int tid = threadIdx.x;
-  const int wv = tid >> 6, ln = tid & 63;
-  const int64_t row = p.row_base + blockIdx.x;
-  if (p.todo != nullptr && p.todo[row] == 0) return;  // ranked by rank_wave_kernel
-  const int64_t orow = p.row_map ? p.row_map[row] : row;
-  const int64_t u = orow + p.offset;
-  const T *srow = static_cast<const T *>(p.scores) + row * p.n_items;
-  RowOut res{0, 0, 0, 0, 0, 0, 0};
-  const int gb = p.retrieve ? 0 : p.gt_ptr[u], ge = p.retrieve ? 0 : p.gt_ptr[u + 1];
-  const int n_gt = ge - gb;
-  int32_t *rec_row = p.rec_out + orow * p.cutoff;
-  for (int i = tid; i < p.cutoff; i += NT) rec_row[i] = -1;
-  if (n_gt == 0 && !p.retrieve) {  // counted in total_user only (:316-321)
-    if (tid == 0) p.out[orow] = res;
-    return;
-  }
-  // what the last phase needs from HBM is requested now, so that its latency hides behind
-  // the ranking: a short ground-truth row, the discounts, the ideal dcg
-  int32_t gt_pref = -1;
-  double disc_pref = 0.0, idcg_pref = 0.0;
-  if (!p.retrieve) {
-    if (n_gt <= 64 && ln < n_gt) gt_pref = p.gt_idx[gb + ln];
-    if (ln < min(p.cutoff, 64)) disc_pref = p.disc[ln];
-    idcg_pref = p.idcg_prefix[min(n_gt, p.cutoff)];
-  }
-  // candidate list
-  int64_t cb = 0, n_cand = p.n_items;
-  const int32_t *list = nullptr;
-  if (p.rec_mode == 1) {
-    cb = p.rec_ptr[0];
-    n_cand = p.rec_ptr[1] - cb;
-    list = p.rec_items + cb;
-  } else if (p.rec_mode == 2) {
-    cb = p.rec_ptr[u];
-    n_cand = p.rec_ptr[u + 1] - cb;
-    list = p.rec_items + cb;
-  }
-  auto item_of = [&](int64_t j) -> int32_t { return list ? list[j] : static_cast<int32_t>(j); };
-  auto sel_of = [&](int64_t j) -> int32_t {  // what a selected entry carries (and ties are ordered by)
-    if constexpr (POS) return static_cast<int32_t>(j);
-    else return item_of(j);
-  };
-  auto key_from_scores = [&](int64_t j) -> uint64_t {
-    const T s = srow[item_of(j)];
-    return is_neg_inf(s) ? KEY_SKIP : order_key(s);
-  };
-  auto key_at = [&](int64_t j) -> uint64_t {
-    return CACHED ? static_cast<uint64_t>(keys[j]) : key_from_scores(j);
-  };
-
-  // --- count rankable candidates (and fill the key cache).  Eight independent loads per
-  //     thread are issued before the first use (clamped index, result masked) so the one
-  //     pass over the scores in HBM is not a chain of exposed latencies.
-  const int64_t span = ((n_cand + NT - 1) / NT) * 64;
-  const int64_t wbeg = wv * span, wend = min<int64_t>(wbeg + span, n_cand);
-  KeyT kreg[MODE == 2 ? MAXQ : 1];
-  int local = 0;
-  uint64_t tmax = 0;  // best rankable key of this thread (0: none)
-  if constexpr (MODE == 2) {
-#pragma unroll
-    for (int qb = 0; qb < MAXQ; qb += 8) {  // eight loads in flight, small register peak
-      T sv[8];
-#pragma unroll
-      for (int q = 0; q < 8; q++)
-        sv[q] = srow[item_of(max<int64_t>(min<int64_t>(wbeg + 64 * (qb + q) + ln, n_cand - 1), 0))];
-#pragma unroll
-      for (int q = 0; q < 8; q++) {
-        const bool live = wbeg + 64 * (qb + q) + ln < wend;
-        const uint64_t k = (!live || is_neg_inf(sv[q])) ? KEY_SKIP : order_key(sv[q]);
-        kreg[qb + q] = static_cast<KeyT>(k);
-        local += k != KEY_SKIP;
-        tmax = (k != KEY_SKIP && k > tmax) ? k : tmax;
-      }
-    }
-  } else {
-    for (int64_t base = 0; base < n_cand; base += NT * 8) {
-      T sv[8];
-#pragma unroll
-      for (int q = 0; q < 8; q++)
-        sv[q] = srow[item_of(min<int64_t>(base + q * NT + tid, n_cand - 1))];
-#pragma unroll
-      for (int q = 0; q < 8; q++) {
-        const int64_t j = base + q * NT + tid;
-        if (j < n_cand) {
-          const uint64_t k = is_neg_inf(sv[q]) ? KEY_SKIP : order_key(sv[q]);
-          if (CACHED) keys[j] = static_cast<KeyT>(k);
-          local += k != KEY_SKIP;
-          tmax = (k != KEY_SKIP && k > tmax) ? k : tmax;
-        }
-      }
-    }
-  }
-  // visit every slot of this wave, all lanes together (f may use wave-wide ballots); f
-  // returns false to stop early (a wave-uniform decision)
-  auto for_each_slot = [&](auto &&f) {
-    if constexpr (MODE == 2) {
-      bool go = true;
-#pragma unroll
-      for (int q = 0; q < MAXQ; q++)
-        if (go && wbeg + 64 * q < wend) go = f(wbeg + 64 * q + ln, static_cast<uint64_t>(kreg[q]));
-    } else {
-      for (int64_t base = wbeg; base < wend; base += 64) {
-        const int64_t j = base + ln;
-        if (!f(j, j < wend ? key_at(j) : KEY_SKIP)) break;
-      }
-    }
-  };
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) local += __shfl_xor(local, o, 64);
-  if (ln == 0) scan_buf[wv] = local;
-  if (tid < 256) hist[tid] = 0;
-  __syncthreads();
-  int n_rankable = 0;
-  for (int w = 0; w < NWV; w++) n_rankable += scan_buf[w];
-  __syncthreads();
-  const int n_rec = min(p.cutoff, n_rankable);
-  res.valid = 1;
-  res.n_rec = n_rec;
-  if (n_rec == 0) {  // :132-135
-    if (tid == 0) p.out[orow] = res;
-    return;
-  }
-
-  // --- short lists (the usual cutoffs): the n_rec-th largest of the per-thread maxima is a
-  //     lower bound L of the n_rec-th largest key (those maxima are n_rec different keys
-  //     >= L).  L costs a radix select over ONE key per thread, and the keys >= L - the
-  //     n_rec winners, all their ties and a few more - are gathered in one sweep and
-  //     sorted exactly by (key desc, index asc) below.  Rows where that list does not fit
-  //     (e.g. thousands of equal scores) take the general selection.
-  constexpr int BITS = KeyBits<T>::value;
-  int n_sel = n_rec;  // entries in sel_key / sel_idx; the best n_rec of them are the result
-  bool fast = n_rec <= NT;
-  if (fast) {
-    uint64_t lpre = 0;
-    int lneed = n_rec;
-    for (int shift = BITS - 8; shift >= 0; shift -= 8) {
-      const uint64_t hi_mask = (shift + 8 >= 64) ? 0ull : (~0ull << (shift + 8));
-      const bool in = (tmax & hi_mask) == (lpre & hi_mask);
-      const uint32_t digit = static_cast<uint32_t>(tmax >> shift) & 0xffu;
-      const unsigned long long todo = __ballot(in);
-      if (todo) {
-        const int leader = __ffsll(static_cast<long long>(todo)) - 1;
-        const uint32_t d = __builtin_amdgcn_readlane(digit, leader);
-        const unsigned long long same = __ballot(in && digit == d);
-        if (same == todo) {
-          if (ln == leader) atomicAdd(&hist[d], static_cast<uint32_t>(__popcll(same)));
-        } else if (in) {
-          atomicAdd(&hist[digit], 1u);
-        }
-      }
-      __syncthreads();
-      int bin = 0, incl = 0;
-      if (tid < 256) {
-        bin = static_cast<int>(hist[255 - tid]);
-        incl = bin;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const int t = __shfl_up(incl, o, 64);
-          if (ln >= o) incl += t;
-        }
-        if (ln == 63) scan_buf[wv] = incl;
-      }
-      __syncthreads();
-      if (tid < 256) {
-        for (int w = 0; w < wv && w < 4; w++) incl += scan_buf[w];
-        if (incl - bin < lneed && incl >= lneed) {
-          sh_prefix = lpre | (static_cast<uint64_t>(255 - tid) << shift);
-          sh_need = (incl == lneed) ? -1 : lneed - (incl - bin);
-        }
-        hist[tid] = 0;
-      }
-      __syncthreads();
-      lpre = sh_prefix;
-      lneed = sh_need;
-      if (lneed < 0) break;  // the whole bin is wanted: its lowest possible key bounds L
-    }
-    const uint64_t L = lpre;
-    if (tid == 0) sh_count = 0;
-    __syncthreads();
-    for_each_slot([&](int64_t j, uint64_t k) {
-      if (k != KEY_SKIP && k >= L) {
-        const int pos = atomicAdd(&sh_count, 1);
-        if (pos < sel_cap) {
-          sel_key[pos] = k;
-          sel_idx[pos] = sel_of(j);
-        }
-      }
-      return true;
-    });
-    __syncthreads();
-    n_sel = sh_count;
-    fast = n_sel <= sel_cap;
-    __syncthreads();  // sh_count is reset by the general selection
-  }
-  if (!fast) {
-  n_sel = n_rec;
-  // --- radix select: key of the n_rec-th best candidate
-  uint64_t prefix = 0;
-  int need = n_rec;  // how many still to take among keys matching `prefix` so far
-  bool inclusive = false;  // true: every key >= prefix is taken and there is no tie pick
-  // hist is zero here (cleared before the count barrier) and is cleared again by the bin scan
-  // of every pass: three barriers per digit
-  for (int shift = BITS - 8; shift >= 0; shift -= 8) {
-    const uint64_t hi_mask = (shift + 8 >= 64) ? 0ull : (~0ull << (shift + 8));
-    for_each_slot([&](int64_t, uint64_t k) {
-      const bool in = k != KEY_SKIP && (k & hi_mask) == (prefix & hi_mask);
-      const uint32_t digit = static_cast<uint32_t>(k >> shift) & 0xffu;
-      // scores share their leading byte(s): when all candidate lanes of a wave fall into
-      // one bin a single lane adds the count (no same-address atomic storm); otherwise
-      // the digits are spread and per-lane atomics are cheap
-      const unsigned long long todo = __ballot(in);
-      if (todo) {
-        const int leader = __ffsll(static_cast<long long>(todo)) - 1;
-        const uint32_t d = __builtin_amdgcn_readlane(digit, leader);
-        const unsigned long long same = __ballot(in && digit == d);
-        if (same == todo) {
-          if (ln == leader) atomicAdd(&hist[d], static_cast<uint32_t>(__popcll(same)));
-        } else if (in) {
-          atomicAdd(&hist[digit], 1u);
-        }
-      }
-      return true;
-    });
-    __syncthreads();
-    // the digit d with  #(digits > d) < need <= #(digits >= d): bins scanned in descending
-    // order by the first four waves
-    int bin = 0, incl = 0;
-    if (tid < 256) {
-      bin = static_cast<int>(hist[255 - tid]);
-      incl = bin;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o, 64);
-        if (ln >= o) incl += t;
-      }
-      if (ln == 63) scan_buf[wv] = incl;
-    }
-    __syncthreads();
-    if (tid < 256) {
-      for (int w = 0; w < wv; w++) incl += scan_buf[w];
-      if (incl - bin < need && incl >= need) {
-        sh_prefix = prefix | (static_cast<uint64_t>(255 - tid) << shift);
-        // the whole bin is wanted: no lower digit has to be resolved (-1 stops the loop)
-        sh_need = (incl == need) ? -1 : need - (incl - bin);
-      }
-      hist[tid] = 0;  // every bin was read before the barrier above
-    }
-    __syncthreads();
-    // (the next write to sh_prefix / sh_need sits two barriers ahead: no barrier after the read)
-    prefix = sh_prefix;
-    need = sh_need;
-    if (need < 0) {
-      inclusive = true;
-      need = 0;
-      break;
-    }
-  }
-  const uint64_t thr = prefix;  // threshold key; `need` ties at thr are taken, lowest index first
-
-  // --- gather winners ((wave, slot, lane) order is index order): sweep 1 appends the keys
-  //     above the threshold and counts the wave's ties, sweep 2 gives the `need` lowest-index
-  //     ties their slots (evaluator.cpp:329, 353-355)
-  if (tid == 0) sh_count = 0;
-  __syncthreads();
-  int my_ties = 0;
-  for_each_slot([&](int64_t j, uint64_t k) {
-    bool tie = false;
-    if (k != KEY_SKIP) {
-      if (inclusive ? k >= thr : k > thr) {
-        const int pos = atomicAdd(&sh_count, 1);
-        sel_key[pos] = k;
-        sel_idx[pos] = sel_of(j);
-      } else if (k == thr) {
-        tie = true;
-      }
-    }
-    my_ties += __popcll(__ballot(tie));
-    return true;
-  });
-  if (ln == 0) scan_buf[wv] = my_ties;
-  __syncthreads();
-  int seen = 0;
-  for (int w = 0; w < wv; w++) seen += scan_buf[w];
-  for_each_slot([&](int64_t j, uint64_t k) {
-    if (seen >= need) return false;
-    const bool tie = k != KEY_SKIP && k == thr;
-    const unsigned long long bal = __ballot(tie);
-    const int rank = seen + __popcll(bal & ((1ull << ln) - 1ull));
-    if (tie && rank < need) {
-      const int pos = atomicAdd(&sh_count, 1);
-      sel_key[pos] = k;
-      sel_idx[pos] = sel_of(j);
-    }
-    seen += __popcll(bal);
-    return true;
-  });
-  __syncthreads();
-  }  // general selection
-  if (n_sel <= 64) {
-    // --- common cutoffs: one wave finishes the row without further barriers.  Lane i holds
-    //     candidate i (the best n_rec of the n_sel gathered ones are the list); bitonic network
-    //     over the lanes (key desc, index asc), hits by binary search, then the sequential
-    //     dcg / AP recurrences of Metrics::update (:136-165).
-    if (wv != 0) return;
-    uint64_t mk = ln < n_sel ? sel_key[ln] : 0ull;
-    int32_t mi = ln < n_sel ? sel_idx[ln] : 0x7fffffff;
-#pragma unroll
-    for (int k2 = 2; k2 <= 64; k2 <<= 1) {
-#pragma unroll
-      for (int j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
-        const uint64_t ok = __shfl_xor(static_cast<unsigned long long>(mk), j2, 64);
-        const int32_t oi = __shfl_xor(mi, j2, 64);
-        const bool mine_first = (mk != ok) ? mk > ok : mi < oi;
-        const bool lower = (ln & j2) == 0, up = (ln & k2) == 0;
-        const bool keep = (lower == up) ? mine_first : !mine_first;
-        mk = keep ? mk : ok;
-        mi = keep ? mi : oi;
-      }
-    }
-    if (p.retrieve) {
-      if (ln < n_rec) rec_row[ln] = POS ? item_of(mi) : mi;
-      return;
-    }
-    bool hit = false;
-    if (ln < n_rec) rec_row[ln] = mi;  // (counted by item_hist_kernel, :146)
-    if (n_gt <= 64) {
-      // short ground-truth row (prefetched at kernel start): compare against every entry
-      // instead of a chain of dependent loads
-      for (int c = 0; c < n_gt; c++) hit |= __builtin_amdgcn_readlane(gt_pref, c) == mi;
-      hit = hit && ln < n_rec;
-    } else if (ln < n_rec) {
-      int lo = gb, hi = ge;
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (p.gt_idx[mid] < mi) lo = mid + 1; else hi = mid;
-      }
-      hit = lo < ge && p.gt_idx[lo] == mi;
-    }
-    const double disc_l = ln < n_rec ? disc_pref : 0.0;
-    unsigned long long hits = __ballot(hit);
-    double dcg = 0, ap = 0;
-    int cum_hit = 0;
-    while (hits) {  // ascending rank order, like the reference's loop over the list
-      const int i = __ffsll(static_cast<long long>(hits)) - 1;
-      hits &= hits - 1;
-      dcg += __shfl(disc_l, i, 64);
-      cum_hit++;
-      ap += static_cast<double>(cum_hit) / (i + 1);
-    }
-    const double idcg = min(n_gt, n_rec) == min(n_gt, p.cutoff)
-                            ? idcg_pref
-                            : p.idcg_prefix[min(n_gt, n_rec)];
-    res.hit = cum_hit > 0 ? 1.0 : 0.0;
-    res.precision = cum_hit / static_cast<double>(n_rec);
-    res.recall = cum_hit / static_cast<double>(
-                               p.recall_with_cutoff ? (n_gt > n_rec ? n_rec : n_gt) : n_gt);
-    res.ndcg = dcg / idcg;
-    res.map = ap / n_gt;
-    if (ln == 0) p.out[orow] = res;
-    return;
-  }
-  // --- bitonic sort of the n_sel gathered candidates: key desc, index asc
-  int n_pow = 1;
-  while (n_pow < n_sel) n_pow <<= 1;
-  for (int i = n_sel + tid; i < n_pow; i += NT) {
-    sel_key[i] = 0ull;
-    sel_idx[i] = 0x7fffffff;
-  }
-  __syncthreads();
-  auto before = [&](int a, int b) {  // element a ranks before element b
-    if (sel_key[a] != sel_key[b]) return sel_key[a] > sel_key[b];
-    return sel_idx[a] < sel_idx[b];
-  };
-  for (int k2 = 2; k2 <= n_pow; k2 <<= 1) {
-    for (int j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
-      for (int i = tid; i < n_pow; i += NT) {
-        const int l = i ^ j2;
-        if (l > i) {
-          const bool up = (i & k2) == 0;
-          const bool swap = up ? before(l, i) : before(i, l);
-          if (swap) {
-            const uint64_t tk = sel_key[i];
-            sel_key[i] = sel_key[l];
-            sel_key[l] = tk;
-            const int32_t ti = sel_idx[i];
-            sel_idx[i] = sel_idx[l];
-            sel_idx[l] = ti;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
-  if (p.retrieve) {
-    for (int i = tid; i < n_rec; i += NT) rec_row[i] = POS ? item_of(sel_idx[i]) : sel_idx[i];
-    return;
-  }
-  // --- hits, histogram, output list
-  for (int i = tid; i < n_rec; i += NT) {
-    const int32_t it = sel_idx[i];
-    rec_row[i] = it;  // (counted by item_hist_kernel, :146)
-    int lo = gb, hi = ge;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (p.gt_idx[mid] < it) lo = mid + 1; else hi = mid;
-    }
-    sel_hit[i] = (lo < ge && p.gt_idx[lo] == it) ? 1 : 0;
-  }
-  __syncthreads();
-  if (wv == 0) {
-    // Metrics::update :136-165 in the same sequential order: the wave reads 64 hit flags at a
-    // time and walks the set bits in ascending rank (every lane carries the same sums)
-    double dcg = 0, ap = 0;
-    int cum_hit = 0;
-    for (int base = 0; base < n_rec; base += 64) {
-      unsigned long long hits = __ballot(base + ln < n_rec && sel_hit[base + ln] != 0);
-      while (hits) {
-        const int i = base + __ffsll(static_cast<long long>(hits)) - 1;
-        hits &= hits - 1;
-        dcg += p.disc[i];
-        cum_hit++;
-        ap += static_cast<double>(cum_hit) / (i + 1);
-      }
-    }
-    const double idcg = p.idcg_prefix[min(n_gt, n_rec)];
-    res.hit = cum_hit > 0 ? 1.0 : 0.0;
-    res.precision = cum_hit / static_cast<double>(n_rec);
-    res.recall = cum_hit / static_cast<double>(
-                               p.recall_with_cutoff ? (n_gt > n_rec ? n_rec : n_gt) : n_gt);
-    res.ndcg = dcg / idcg;
-    res.map = ap / n_gt;
-    if (ln == 0) p.out[orow] = res;
-  }
-}
-
-}  // namespace eval
-}  // namespace irs
+// the kernels, in this order (each header names what it needs from the ones before it)
+#include "eval_rank_kernels.hpp"
 #include "eval_fused_kernels.hpp"
-namespace irs {
-namespace eval {
-
-// ---------------------------------------------------------------------------
-// One WAVE per user row, one pass over the scores, no barrier and no LDS: the usual case
-// (every item is a candidate, cutoff <= 64).  Lane l streams the scores l, l + 64, ... with
-// U loads in flight and keeps its own M best (key, index) pairs sorted in registers.  The
-// list is then drawn from the 64 heads: a wave-wide arg-max of (key desc, index asc) per
-// rank, the winning lane popping its head; lane i ends up with rank i, exactly the state the
-// single-wave finish of rank_rows_kernel starts from.  A lane that runs dry although it saw
-// more than M rankable scores may hide a better candidate: the row is then flagged in p.todo
-// and ranked by rank_rows_kernel (for cutoff 20 and M = 4 about one row in a thousand).
-// 8 waves per SIMD are resident, so the loads of some rows overlap the drawing of others.
-// Last phase of a wave-ranked row: lane i holds the item of rank i (mi, i < n_rec).  Hits,
-// then the SEQUENTIAL dcg / AP recurrences of Metrics::update (evaluator.cpp:136-165) so that
-// the fp64 terms are those of the reference.
-__device__ __forceinline__ void wave_metrics_tail(const EvalParams &p, int64_t row, int ln,
-                                                  int32_t mi, int n_rec, int gb, int ge, int n_gt,
-                                                  int32_t gt_pref, double disc_pref,
-                                                  double idcg_pref, RowOut res, int32_t *rec_row) {
-  if (p.retrieve) {
-    if (ln < n_rec) rec_row[ln] = mi;
-    return;
-  }
-  bool hit = false;
-  if (ln < n_rec) rec_row[ln] = mi;  // (counted by item_hist_kernel, :146)
-  if (n_gt <= 64) {
-    for (int c = 0; c < n_gt; c++) hit |= __builtin_amdgcn_readlane(gt_pref, c) == mi;
-    hit = hit && ln < n_rec;
-  } else if (ln < n_rec) {
-    int lo = gb, hi = ge;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (p.gt_idx[mid] < mi) lo = mid + 1; else hi = mid;
-    }
-    hit = lo < ge && p.gt_idx[lo] == mi;
-  }
-  const double disc_l = ln < n_rec ? disc_pref : 0.0;
-  unsigned long long hits = __ballot(hit);
-  double dcg = 0, ap = 0;
-  int cum_hit = 0;
-  while (hits) {  // ascending rank order, like the reference's loop over the list (:136-165)
-    const int i = __ffsll(static_cast<long long>(hits)) - 1;
-    hits &= hits - 1;
-    dcg += __shfl(disc_l, i, 64);
-    cum_hit++;
-    ap += static_cast<double>(cum_hit) / (i + 1);
-  }
-  const double idcg = min(n_gt, n_rec) == min(n_gt, p.cutoff) ? idcg_pref
-                                                              : p.idcg_prefix[min(n_gt, n_rec)];
-  res.hit = cum_hit > 0 ? 1.0 : 0.0;
-  res.precision = cum_hit / static_cast<double>(n_rec);
-  res.recall = cum_hit / static_cast<double>(
-                             p.recall_with_cutoff ? (n_gt > n_rec ? n_rec : n_gt) : n_gt);
-  res.ndcg = dcg / idcg;
-  res.map = ap / n_gt;
-  if (ln == 0) p.out[row] = res;
-}
-
-// Emit path, last kernel: one wave per user ranks its candidate list (score_emit_kernel:
-// every unmasked item with score >= tau_u, in arbitrary order) by (score desc, index asc).
-// Lane l keeps the M best of the entries l, l + 64, ... sorted in registers, the list is drawn
-// from the 64 heads; a lane that runs dry with entries left over may hide a better one: the row
-// is then ranked by rank_cand_slow_kernel.
-template <int M>
-__global__ __launch_bounds__(256) void rank_cand_kernel(EvalParams p, EmitParams f,
-                                                        const int32_t *__restrict__ n_masked) {
-  const int ln = threadIdx.x & 63;
-  const int64_t row = static_cast<int64_t>(blockIdx.x) * 4 + wave_index_in_block();
-  if (row >= p.rows) return;
-  const int64_t u = row + p.offset;
-  RowOut res{0, 0, 0, 0, 0, 0, 0};
-  const int gb = p.gt_ptr[u], ge = p.gt_ptr[u + 1];
-  const int n_gt = ge - gb;
-  int32_t *rec_row = p.rec_out + row * p.cutoff;
-  if (ln < p.cutoff) rec_row[ln] = -1;  // cutoff <= 32
-  if (ln == 0) p.todo[row] = 0;
-  if (n_gt == 0) {  // counted in total_user only (:316-321)
-    if (ln == 0) p.out[row] = res;
-    return;
-  }
-  int32_t gt_pref = -1;
-  double disc_pref = 0.0;
-  if (n_gt <= 64 && ln < n_gt) gt_pref = p.gt_idx[gb + ln];
-  if (ln < p.cutoff) disc_pref = p.disc[ln];
-  const double idcg_pref = p.idcg_prefix[min(n_gt, p.cutoff)];
-  if (f.hard[row]) return;  // ranked from its full score row afterwards
-  const int n = min(f.cand_cnt[row], EM_CAP);
-  const int64_t n_rankable = f.n_items - (n_masked ? n_masked[row] : 0);
-  const int n_rec = static_cast<int>(min<int64_t>(p.cutoff, n_rankable));
-  res.valid = 1;
-  res.n_rec = n_rec;
-  if (n_rec == 0) {  // :132-135
-    if (ln == 0) p.out[row] = res;
-    return;
-  }
-  if (n < n_rec) {  // cannot happen with a valid threshold: have the host repeat the call
-    if (ln == 0) atomicOr(f.bad_flag, 2);
-    if (ln == 0) p.out[row] = res;
-    return;
-  }
-  const float NEG_INF = -std::numeric_limits<float>::infinity();
-  const float *cs = f.cand_score + static_cast<size_t>(row) * EM_CAP;
-  const int32_t *ci = f.cand_item + static_cast<size_t>(row) * EM_CAP;
-  if (n <= 64) {
-    // The usual case after pruning (a few dozen candidates): one candidate per lane, its rank
-    // = the number of candidates that go before it (score desc, index asc: a strict order, so
-    // the ranks are a permutation), counted against every candidate by v_readlane; the item
-    // of rank r is then pushed to lane r.
-    const float s = ln < n ? cs[ln] : NEG_INF;
-    const int32_t i = ln < n ? ci[ln] : 0x7fffffff;
-    int rank = 0;
-    for (int k = 0; k < n; k++) {  // n is wave-uniform
-      const float sk = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, s), k));
-      const int32_t ik = __builtin_amdgcn_readlane(i, k);
-      rank += (sk > s || (sk == s && ik < i)) ? 1 : 0;
-    }
-    if (ln >= n) rank = ln;  // lanes without a candidate keep to themselves
-    const int32_t mi = __builtin_amdgcn_ds_permute(rank << 2, i);
-    wave_metrics_tail(p, row, ln, mi, n_rec, gb, ge, n_gt, gt_pref, disc_pref, idcg_pref, res, rec_row);
-    return;
-  }
-  float bs[M];
-  int32_t bi[M];
-#pragma unroll
-  for (int t = 0; t < M; t++) {
-    bs[t] = NEG_INF;
-    bi[t] = 0x7fffffff;
-  }
-  for (int e0 = 0; e0 < n; e0 += 64) {
-    const int e = e0 + ln;
-    float s = e < n ? cs[e] : NEG_INF;
-    int32_t i = e < n ? ci[e] : 0x7fffffff;
-#pragma unroll
-    for (int t = 0; t < M; t++) {
-      const bool better = s > bs[t] || (s == bs[t] && i < bi[t]);
-      const float ts = bs[t];
-      const int32_t ti = bi[t];
-      bs[t] = better ? s : ts;
-      bi[t] = better ? i : ti;
-      s = better ? ts : s;
-      i = better ? ti : i;
-    }
-  }
-  const int mine_total = (n - ln + 63) / 64;  // entries this lane has seen
-  int32_t mi = 0x7fffffff;
-  int popped = 0;
-  for (int it = 0; it < n_rec; it++) {
-    float ws = bs[0];
-    int32_t wi = bi[0];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      const float os = __shfl_xor(ws, o, 64);
-      const int32_t oi = __shfl_xor(wi, o, 64);
-      const bool better = os > ws || (os == ws && oi < wi);
-      ws = better ? os : ws;
-      wi = better ? oi : wi;
-    }
-    if (ln == it) mi = wi;
-    if (bi[0] == wi && bs[0] == ws) {  // item ids are unique: one lane
-#pragma unroll
-      for (int t = 0; t + 1 < M; t++) {
-        bs[t] = bs[t + 1];
-        bi[t] = bi[t + 1];
-      }
-      bs[M - 1] = NEG_INF;
-      bi[M - 1] = 0x7fffffff;
-      popped++;
-    }
-    if (it + 1 < n_rec && __any(popped == M && mine_total > M)) {
-      if (ln == 0) p.todo[row] = 1;
-      return;
-    }
-  }
-  wave_metrics_tail(p, row, ln, mi, n_rec, gb, ge, n_gt, gt_pref, disc_pref, idcg_pref, res, rec_row);
-}
-
-// The rows rank_cand_kernel flagged: exact rank of every candidate by counting (LDS copy).
-__global__ __launch_bounds__(256) void rank_cand_slow_kernel(EvalParams p, EmitParams f,
-                                                             const int32_t *__restrict__ n_masked) {
-  __shared__ float cs[4][EM_CAP];
-  __shared__ int32_t ci[4][EM_CAP];
-  __shared__ int32_t sel[4][64];
-  const int ln = threadIdx.x & 63, wv = wave_index_in_block();
-  const int64_t row = static_cast<int64_t>(blockIdx.x) * 4 + wv;
-  if (row >= p.rows || p.todo[row] == 0) return;
-  const int64_t u = row + p.offset;
-  RowOut res{0, 0, 0, 0, 0, 0, 0};
-  const int gb = p.gt_ptr[u], ge = p.gt_ptr[u + 1];
-  const int n_gt = ge - gb;
-  int32_t *rec_row = p.rec_out + row * p.cutoff;
-  int32_t gt_pref = -1;
-  double disc_pref = 0.0;
-  if (n_gt <= 64 && ln < n_gt) gt_pref = p.gt_idx[gb + ln];
-  if (ln < p.cutoff) disc_pref = p.disc[ln];
-  const double idcg_pref = p.idcg_prefix[min(n_gt, p.cutoff)];
-  const int n = min(f.cand_cnt[row], EM_CAP);
-  const int64_t n_rankable = f.n_items - (n_masked ? n_masked[row] : 0);
-  const int n_rec = static_cast<int>(min<int64_t>(p.cutoff, n_rankable));
-  res.valid = 1;
-  res.n_rec = n_rec;
-  for (int e = ln; e < n; e += 64) {
-    cs[wv][e] = f.cand_score[static_cast<size_t>(row) * EM_CAP + e];
-    ci[wv][e] = f.cand_item[static_cast<size_t>(row) * EM_CAP + e];
-  }
-  __threadfence_block();
-  for (int e = ln; e < n; e += 64) {
-    const float s = cs[wv][e];
-    const int32_t i = ci[wv][e];
-    int rank = 0;
-    for (int k = 0; k < n; k++) {
-      const float sk = cs[wv][k];
-      const int32_t ik = ci[wv][k];
-      rank += (sk > s || (sk == s && ik < i)) ? 1 : 0;
-    }
-    if (rank < n_rec) sel[wv][rank] = i;
-  }
-  __threadfence_block();
-  const int32_t mi = ln < n_rec ? sel[wv][ln] : 0x7fffffff;
-  wave_metrics_tail(p, row, ln, mi, n_rec, gb, ge, n_gt, gt_pref, disc_pref, idcg_pref, res, rec_row);
-}
-
-template <class T, int M>
-__global__ __launch_bounds__(256) void rank_wave_kernel(EvalParams p) {
-  constexpr int U = 16;
-  const int ln = threadIdx.x & 63;
-  const int64_t row = static_cast<int64_t>(blockIdx.x) * 4 + wave_index_in_block();
-  if (row >= p.rows) return;
-  const int64_t orow = p.row_map ? p.row_map[row] : row;
-  const int64_t u = orow + p.offset;
-  const T *srow = static_cast<const T *>(p.scores) + row * p.n_items;
-  RowOut res{0, 0, 0, 0, 0, 0, 0};
-  const int gb = p.retrieve ? 0 : p.gt_ptr[u], ge = p.retrieve ? 0 : p.gt_ptr[u + 1];
-  const int n_gt = ge - gb;
-  int32_t *rec_row = p.rec_out + orow * p.cutoff;
-  if (ln < p.cutoff) rec_row[ln] = -1;  // cutoff <= 64
-  if (ln == 0) p.todo[row] = 0;
-  if (n_gt == 0 && !p.retrieve) {  // counted in total_user only (:316-321)
-    if (ln == 0) p.out[orow] = res;
-    return;
-  }
-  int32_t gt_pref = -1;
-  double disc_pref = 0.0, idcg_pref = 0.0;
-  if (!p.retrieve) {
-    if (n_gt <= 64 && ln < n_gt) gt_pref = p.gt_idx[gb + ln];
-    if (ln < p.cutoff) disc_pref = p.disc[ln];
-    idcg_pref = p.idcg_prefix[min(n_gt, p.cutoff)];
-  }
-  // The lists hold the raw scores: float comparison is the reference's order (-0.0 == +0.0
-  // ties; equal scores keep index order because insertion is strict), -inf marks an empty
-  // slot and is never inserted - exactly the scores that are not rankable.  A NaN (ranks last
-  // among the rankable, evaluator.hip header) would never be inserted either, so a row that
-  // contains one goes to the general kernel.
-  const T NEG_INF = -std::numeric_limits<T>::infinity();
-  T bs[M];
-  int32_t bi[M];
-#pragma unroll
-  for (int t = 0; t < M; t++) {
-    bs[t] = NEG_INF;
-    bi[t] = 0x7fffffff;
-  }
-  int n_rankable = 0;             // wave-uniform
-  unsigned long long nan_any = 0;  // lanes that met a NaN
-  const int32_t n = static_cast<int32_t>(p.n_items);
-  auto insert = [&](T cs, int32_t ci) {
-    if (__any(cs > bs[M - 1])) {
-      // from the first entry the new score beats, the tail SHIFTS down one place (sticky
-      // `gt`): an entry pushed down by one place still goes before its equals, whose
-      // indices are higher
-      bool gt = false;
-#pragma unroll
-      for (int t = 0; t < M; t++) {
-        gt = gt || cs > bs[t];
-        const T ts = bs[t];
-        const int32_t ti = bi[t];
-        bs[t] = gt ? cs : ts;
-        bi[t] = gt ? ci : ti;
-        cs = gt ? ts : cs;
-        ci = gt ? ti : ci;
-      }
-    }
-  };
-  int32_t base = 0;
-  for (; base + 64 * U <= n; base += 64 * U) {  // full groups: no bounds to check
-    const T *sp = srow + base + ln;
-    T sv[U];
-#pragma unroll
-    for (int q = 0; q < U; q++) sv[q] = sp[64 * q];
-#pragma unroll
-    for (int q = 0; q < U; q++) {
-      nan_any |= __ballot(sv[q] != sv[q]);
-      n_rankable += __popcll(__ballot(sv[q] != NEG_INF));
-      insert(sv[q], base + 64 * q + ln);
-    }
-  }
-  if (base < n) {  // the last, partial group
-    T sv[U];
-#pragma unroll
-    for (int q = 0; q < U; q++) sv[q] = srow[min(base + 64 * q + ln, n - 1)];
-#pragma unroll
-    for (int q = 0; q < U; q++) {
-      const int32_t j = base + 64 * q + ln;
-      const T s1 = j < n ? sv[q] : NEG_INF;
-      nan_any |= __ballot(s1 != s1);
-      n_rankable += __popcll(__ballot(s1 != NEG_INF));
-      insert(s1, j);
-    }
-  }
-  if (nan_any) {
-    if (ln == 0) p.todo[row] = 1;
-    return;
-  }
-  const int n_rec = min(p.cutoff, n_rankable);
-  res.valid = 1;
-  res.n_rec = n_rec;
-  if (n_rec == 0) {  // :132-135
-    if (ln == 0) p.out[orow] = res;
-    return;
-  }
-  // --- draw the list: rank `it` is the best head
-  int32_t mi = 0x7fffffff;
-  int popped = 0;
-  for (int it = 0; it < n_rec; it++) {
-    T ws = bs[0];
-    int32_t wi = bi[0];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      const T os = __shfl_xor(ws, o, 64);
-      const int32_t oi = __shfl_xor(wi, o, 64);
-      const bool better = os > ws || (os == ws && oi < wi);
-      ws = better ? os : ws;
-      wi = better ? oi : wi;
-    }
-    if (ln == it) mi = wi;
-    const bool mine = bi[0] == wi && bs[0] == ws;  // indices are unique: one lane
-    if (mine) {
-#pragma unroll
-      for (int t = 0; t + 1 < M; t++) {
-        bs[t] = bs[t + 1];
-        bi[t] = bi[t + 1];
-      }
-      bs[M - 1] = NEG_INF;
-      bi[M - 1] = 0x7fffffff;
-      popped++;
-    }
-    // a lane that ran dry may hide the next best candidate (it kept only its M best)
-    if (it + 1 < n_rec && __any(popped == M)) {
-      if (ln == 0) p.todo[row] = 1;
-      return;
-    }
-  }
-  wave_metrics_tail(p, orow, ln, mi, n_rec, gb, ge, n_gt, gt_pref, disc_pref, idcg_pref, res, rec_row);
-}
-
-// First level of the sum for large calls: workgroup b folds the rows [b * chunk, (b + 1) * chunk)
-// into one RowOut-like partial with the SAME code as reduce_rows_kernel, so that the second
-// level (reduce over the partials) keeps a fixed order.  See reduce_rows_kernel.
-struct RowPartial {
-  long long valid;
-  double hit, recall, ndcg, precision, map;
-};
-
-// Sum of the per-user terms of one call (one 1024-thread workgroup) in a fixed order, so the
-// fp64 result is reproducible run to run; it is not the strict user order of a
-// single-threaded reference run (the reference's own order depends on n_threads,
-// evaluator.cpp:280-312).
-__global__ __launch_bounds__(1024) void reduce_rows_kernel(const RowOut *rows, int64_t n,
-                                                           irs_metrics *out,
-                                                           RowPartial *partials = nullptr,
-                                                           int64_t chunk = 0) {
-  // thread t adds rows t, t + 1024, ... in that order; the 64 lanes of a wave fold by a fixed
-  // butterfly and wave 0 adds the 16 wave sums in wave order.  With `partials` workgroup b does
-  // that for its chunk of rows only and leaves the sums there (reduce_partials_kernel adds the
-  // chunks in order): one workgroup walking 138 k rows alone took 0.11 ms.
-  __shared__ double part[16][5];
-  __shared__ long long part_valid[16];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  long long valid = 0;
-  double hit = 0, recall = 0, ndcg = 0, precision = 0, map = 0;
-  if (partials) {
-    rows += static_cast<int64_t>(blockIdx.x) * chunk;
-    n = min(chunk, n - static_cast<int64_t>(blockIdx.x) * chunk);
-  }
-  for (int64_t i = tid; i < n; i += 1024) {
-    const RowOut r = rows[i];
-    if (r.valid) {
-      valid += 1;
-      hit += r.hit;
-      recall += r.recall;
-      ndcg += r.ndcg;
-      precision += r.precision;
-      map += r.map;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    valid += __shfl_xor(valid, o, 64);
-    hit += __shfl_xor(hit, o, 64);
-    recall += __shfl_xor(recall, o, 64);
-    ndcg += __shfl_xor(ndcg, o, 64);
-    precision += __shfl_xor(precision, o, 64);
-    map += __shfl_xor(map, o, 64);
-  }
-  if (lane == 0) {
-    part_valid[wv] = valid;
-    part[wv][0] = hit;
-    part[wv][1] = recall;
-    part[wv][2] = ndcg;
-    part[wv][3] = precision;
-    part[wv][4] = map;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    long long v = 0;
-    double acc[5] = {0, 0, 0, 0, 0};
-    for (int w = 0; w < 16; w++) {
-      v += part_valid[w];
-      for (int c = 0; c < 5; c++) acc[c] += part[w][c];
-    }
-    if (partials) {
-      partials[blockIdx.x] = RowPartial{v, acc[0], acc[1], acc[2], acc[3], acc[4]};
-      return;
-    }
-    out->valid_user += v;
-    out->total_user += n;
-    out->hit += acc[0];
-    out->recall += acc[1];
-    out->ndcg += acc[2];
-    out->precision += acc[3];
-    out->map += acc[4];
-  }
-}
-
-__global__ void reduce_partials_kernel(const RowPartial *partials, int nb, int64_t n, irs_metrics *out) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  long long v = 0;
-  double acc[5] = {0, 0, 0, 0, 0};
-  for (int b = 0; b < nb; b++) {  // chunk order
-    v += partials[b].valid;
-    acc[0] += partials[b].hit;
-    acc[1] += partials[b].recall;
-    acc[2] += partials[b].ndcg;
-    acc[3] += partials[b].precision;
-    acc[4] += partials[b].map;
-  }
-  out->valid_user += v;
-  out->total_user += n;
-  out->hit += acc[0];
-  out->recall += acc[1];
-  out->ndcg += acc[2];
-  out->precision += acc[3];
-  out->map += acc[4];
-}
-
-__global__ void merge_partials_kernel(const RowPartial *partials, int nb, int64_t n, irs_metrics *out) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  long long v = out->valid_user;
-  double acc[5] = {out->hit, out->recall, out->ndcg, out->precision, out->map};
-  for (int b = 0; b < nb; b++) {  // chunk order, every chunk onto the running sum
-    v += partials[b].valid;
-    acc[0] += partials[b].hit;
-    acc[1] += partials[b].recall;
-    acc[2] += partials[b].ndcg;
-    acc[3] += partials[b].precision;
-    acc[4] += partials[b].map;
-  }
-  out->valid_user = v;
-  out->total_user += n;
-  out->hit = acc[0];
-  out->recall = acc[1];
-  out->ndcg = acc[2];
-  out->precision = acc[3];
-  out->map = acc[4];
-}
-
-// item_cnt[i] += how often item i stands in the recommended lists of a call (Metrics::update,
-// evaluator.cpp:146).  `rec` = the lists the ranking kernels wrote ([rows, cutoff], -1 where
-// there is no entry).  Everybody's list is full of the same popular items, so one global atomic
-// per entry queues up on a few addresses (1 ms for 2.7 M entries); each workgroup counts its
-// slice in an LDS table first (direct-mapped, a colliding item goes to memory at once) and adds
-// one total per item it met.
-constexpr int HIST_SLOTS = 8192;
-__global__ __launch_bounds__(1024) void item_hist_kernel(const int32_t *__restrict__ rec, int64_t n,
-                                                         unsigned long long *__restrict__ item_cnt) {
-  __shared__ int32_t ids[HIST_SLOTS];
-  __shared__ uint32_t cnt[HIST_SLOTS];
-  for (int i = threadIdx.x; i < HIST_SLOTS; i += 1024) {
-    ids[i] = -1;
-    cnt[i] = 0;
-  }
-  __syncthreads();
-  const int64_t per = (n + gridDim.x - 1) / gridDim.x;
-  const int64_t b = per * blockIdx.x, e = min(b + per, n);
-  for (int64_t i = b + threadIdx.x; i < e; i += 1024) {
-    const int32_t it = rec[i];
-    if (it < 0) continue;
-    const uint32_t slot = (static_cast<uint32_t>(it) * 2654435761u) >> 19;  // 13 bits
-    const int32_t prev = atomicCAS(&ids[slot], -1, it);
-    if (prev == -1 || prev == it) atomicAdd(&cnt[slot], 1u);
-    else atomicAdd(&item_cnt[it], 1ull);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < HIST_SLOTS; i += 1024)
-    if (ids[i] >= 0 && cnt[i] > 0) atomicAdd(&item_cnt[ids[i]], static_cast<unsigned long long>(cnt[i]));
-}
-
-// Catalogues whose counters fit one CU's LDS (n_items <= 36,864; ML-20M: 26,744): a direct table per
-// workgroup - one LDS atomic per entry, no tags, no collisions (the hashed table above sends every
-// collision to a hot global address: 109 us for the 2.8 M entries of an ML-20M call, this form 12).
-constexpr int64_t HIST_DIRECT_MAX = 36864;
-__global__ __launch_bounds__(1024) void item_hist_direct_kernel(const int32_t *__restrict__ rec, int64_t n,
-                                                                int32_t n_items,
-                                                                unsigned long long *__restrict__ item_cnt) {
-  extern __shared__ uint32_t hist_cnt[];
-  for (int i = threadIdx.x; i < n_items; i += 1024) hist_cnt[i] = 0u;
-  __syncthreads();
-  const int64_t per = (n + gridDim.x - 1) / gridDim.x;
-  const int64_t b = per * blockIdx.x, e = min(b + per, n);
-  for (int64_t i = b + threadIdx.x; i < e; i += 1024) {
-    const int32_t it = rec[i];
-    if (it >= 0 && it < n_items) atomicAdd(&hist_cnt[it], 1u);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < n_items; i += 1024) {
-    const uint32_t c = hist_cnt[i];
-    if (c) atomicAdd(&item_cnt[i], static_cast<unsigned long long>(c));
-  }
-}
-
-inline void launch_item_hist(const int32_t *rec, int64_t n, unsigned long long *item_cnt, hipStream_t s,
-                             int64_t n_items = 0) {
-  if (n <= 0) return;
-  if (n_items > 0 && n_items <= HIST_DIRECT_MAX && n >= 65536) {
-    const size_t lds = static_cast<size_t>(n_items) * sizeof(uint32_t);
-    IRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(item_hist_direct_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                static_cast<int>(HIST_DIRECT_MAX * sizeof(uint32_t))));
-    const int64_t grid = std::min<int64_t>(128, (n + 16383) / 16384);
-    hipLaunchKernelGGL(item_hist_direct_kernel, dim3(static_cast<unsigned>(grid)), dim3(1024), lds, s, rec, n,
-                       static_cast<int32_t>(n_items), item_cnt);
-    return;
-  }
-  const int64_t grid = std::min<int64_t>(1024, (n + 16383) / 16384);
-  hipLaunchKernelGGL(item_hist_kernel, dim3(static_cast<unsigned>(grid)), dim3(1024), 0, s, rec, n, item_cnt);
-}
-
-// scores[row, col] = -inf for the stored entries of the mask rows (evaluator.py:426-432)
-// (`n_items` = row stride = number of leading items the block holds: entries beyond are skipped)
-// (`row_list`, when given: score row r is masked with the mask row row_list[r])
-__global__ void mask_rows_kernel(float *scores, int64_t rows, int64_t n_items,
-                                 const int64_t *mask_ptr, const int32_t *mask_idx,
-                                 const int32_t *row_list = nullptr) {
-  const int64_t row = blockIdx.x;
-  if (row >= rows) return;
-  const int64_t mrow = row_list ? row_list[row] : row;
-  for (int64_t q = mask_ptr[mrow] + threadIdx.x; q < mask_ptr[mrow + 1]; q += blockDim.x) {
-    const int32_t j = mask_idx[q];
-    if (j < n_items) scores[row * n_items + j] = -std::numeric_limits<float>::infinity();
-  }
-}
-
-// the same for a block of either score type whose mask rows arrive with the call
-// (irs_eval_get_metrics_masked): mask_ptr is relative to the first row of the block
-template <class T>
-__global__ void mask_block_kernel(T *scores, int64_t rows, int64_t n_items,
-                                  const int64_t *mask_ptr, const int32_t *mask_idx) {
-  const int64_t row = blockIdx.x;
-  if (row >= rows) return;
-  for (int64_t q = mask_ptr[row] + threadIdx.x; q < mask_ptr[row + 1]; q += blockDim.x) {
-    const int32_t j = mask_idx[q];
-    if (j >= 0 && j < n_items) scores[row * n_items + j] = -std::numeric_limits<T>::infinity();
-  }
-}
-
-}  // namespace eval
-}  // namespace irs
+#include "eval_cand_kernels.hpp"
+#include "eval_reduce_kernels.hpp"
 #include "eval_sim_kernels.hpp"
 #include "eval_dense_kernels.hpp"
 #include "serve_kernels.hpp"
+#include "eval_fold_kernels.hpp"
 
 using namespace irs;
 using namespace irs::eval;
@@ -1222,35 +107,37 @@ void validate_call(irs_evaluator *e, int64_t rows, int64_t cutoff, int64_t offse
   check_arg(cutoff <= e->n_items, "cutoff must not exeeed the number of items.");
 }
 
+// IRSPACK_AMD_EVAL_WAVE=0: general kernel only (read per call: tests toggle it)
+bool wave_enabled() {
+  const char *e = std::getenv("IRSPACK_AMD_EVAL_WAVE");
+  return !(e && e[0] == '0');
+}
+
 // cutoff > SEL_CAP: the lists of a launch's workgroups in global scratch (13 bytes per entry,
 // big_cap entries per row), at most ~1 GiB of it: the rows go through in launches of
-// `per` rows.  Rare (the reference's callers use cutoffs of 5..100), so the goal is only to be
+// `big_rows` rows.  Rare (the reference's callers use cutoffs of 5..100), so the goal is only to be
 // correct for every cutoff the reference accepts and not slower than its partial_sort.
-template <class T, bool POS = false> void launch_rank_big(EvalParams p, int64_t max_cand, hipStream_t s) {
-  int64_t cap = 1;
-  while (cap < p.cutoff) cap <<= 1;
-  const int64_t per = std::max<int64_t>(1, std::min<int64_t>(p.rows, (int64_t(1) << 30) / (cap * 13)));
+template <class T, bool POS = false> void launch_rank_big(EvalParams p, const RankPlan &r, hipStream_t s) {
   DeviceBuffer<uint64_t> bk;
   DeviceBuffer<int32_t> bi;
   DeviceBuffer<uint8_t> bh;
-  bk.alloc(static_cast<size_t>(per) * cap);
-  bi.alloc(static_cast<size_t>(per) * cap);
-  bh.alloc(static_cast<size_t>(per) * cap);
+  bk.alloc(static_cast<size_t>(r.big_rows) * r.big_cap);
+  bi.alloc(static_cast<size_t>(r.big_rows) * r.big_cap);
+  bh.alloc(static_cast<size_t>(r.big_rows) * r.big_cap);
   p.big_key = bk.ptr;
   p.big_idx = bi.ptr;
   p.big_hit = bh.ptr;
-  p.big_cap = static_cast<int32_t>(cap);
+  p.big_cap = static_cast<int32_t>(r.big_cap);
   p.todo = nullptr;
-  const size_t key_bytes = static_cast<size_t>(std::max<int64_t>(max_cand, 1)) * sizeof(typename KeyStore<T>::type);
-  for (int64_t b = 0; b < p.rows; b += per) {
-    const unsigned m = static_cast<unsigned>(std::min<int64_t>(per, p.rows - b));
+  for (int64_t b = 0; b < p.rows; b += r.big_rows) {
+    const unsigned m = static_cast<unsigned>(std::min<int64_t>(r.big_rows, p.rows - b));
     p.row_base = b;
-    if (key_bytes <= 128 * 1024) {
+    if (r.mode == 1) {
       auto kernel = rank_rows_kernel<T, 1024, 1, RANK_MAXQ, true, POS>;
       IRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  static_cast<int>(key_bytes)));
-      hipLaunchKernelGGL(kernel, dim3(m), dim3(1024), key_bytes, s, p);
+                                  static_cast<int>(r.key_bytes)));
+      hipLaunchKernelGGL(kernel, dim3(m), dim3(1024), r.key_bytes, s, p);
     } else {
       hipLaunchKernelGGL((rank_rows_kernel<T, 256, 0, RANK_MAXQ, true, POS>), dim3(m), dim3(256), 0, s, p);
     }
@@ -1259,53 +146,60 @@ template <class T, bool POS = false> void launch_rank_big(EvalParams p, int64_t 
   IRS_HIP(hipStreamSynchronize(s));  // the scratch is released on return
 }
 
+// Ranks the rows of `p` with the kernels plan_rank names (`todo`: scratch of one flag per row, or null = the
+// general kernel for every row).
 template <class T, bool POS = false> void launch_rank(EvalParams p, int64_t max_cand, hipStream_t s, int32_t *todo) {
-  if (p.cutoff > SEL_CAP) {
-    launch_rank_big<T, POS>(p, max_cand, s);
+  const RankPlan r = plan_rank(p.cutoff, p.rows, max_cand, std::is_same<T, float>::value, p.rec_mode, p.n_items,
+                               wave_enabled(), todo != nullptr);
+  if (r.big) {
+    launch_rank_big<T, POS>(p, r, s);
     return;
   }
-  // the usual case first (all items are candidates, cutoff <= 64): one wave per row; the
-  // rows it flags (and every row otherwise) go through the general kernel
   p.todo = nullptr;
-  const bool wave_ok = [] {  // IRSPACK_AMD_EVAL_WAVE=0: general kernel only (read per call: tests toggle it)
-    const char *e = std::getenv("IRSPACK_AMD_EVAL_WAVE");
-    return !(e && e[0] == '0');
-  }();
-  if (wave_ok && p.rec_mode == 0 && p.cutoff <= 64 && p.n_items < (int64_t(1) << 31) - 64 * 16 &&
-      todo != nullptr) {
+  if (r.wave) {
     p.todo = todo;
     const dim3 grid(static_cast<unsigned>((p.rows + 3) / 4));
-    if (p.cutoff <= 24)
+    if (r.wave_m == 4)
       hipLaunchKernelGGL((rank_wave_kernel<T, 4>), grid, dim3(256), 0, s, p);
     else
       hipLaunchKernelGGL((rank_wave_kernel<T, 8>), grid, dim3(256), 0, s, p);
   }
-  // key cache in LDS when a row's candidates fit next to the 28 KB of static LDS
-  const size_t key_bytes = static_cast<size_t>(std::max<int64_t>(max_cand, 1)) * sizeof(typename KeyStore<T>::type);
-  if (std::is_same<T, float>::value && max_cand <= 1024 * RANK_MAXQ) {
+  if (r.mode == 2) {
     hipLaunchKernelGGL((rank_rows_kernel<T, 1024, 2, RANK_MAXQ, false, POS>), dim3(p.rows), dim3(1024), 0, s, p);
-  } else if (key_bytes <= 128 * 1024) {
+  } else if (r.mode == 1) {
     auto kernel = rank_rows_kernel<T, 1024, 1, RANK_MAXQ, false, POS>;
     IRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                static_cast<int>(key_bytes)));
-    hipLaunchKernelGGL(kernel, dim3(p.rows), dim3(1024), key_bytes, s, p);
+                                static_cast<int>(r.key_bytes)));
+    hipLaunchKernelGGL(kernel, dim3(p.rows), dim3(1024), r.key_bytes, s, p);
   } else {
     hipLaunchKernelGGL((rank_rows_kernel<T, 256, 0, RANK_MAXQ, false, POS>), dim3(p.rows), dim3(256), 0, s, p);
   }
 }
 
-// ranks `rows` rows already resident at `d_scores` and accumulates into out / item_cnt
-// (`running`, when given: the per-user terms are added to `running` in HOST_LOOP_ROWS-row chunks, chunk after
-// chunk, instead of to e->metrics - see CutoffTotals)
-template <class T>
-void rank_block(irs_evaluator *e, const void *d_scores, int64_t rows, int64_t cutoff,
-                int64_t offset, bool rwc, hipStream_t s, irs_metrics *running = nullptr) {
+// item_cnt += the histogram of the `n` list entries at `rec`
+void launch_item_hist(const int32_t *rec, int64_t n, unsigned long long *item_cnt, hipStream_t s, int64_t n_items) {
+  const HistPlan h = plan_item_hist(n, n_items);
+  if (h.grid <= 0) return;
+  if (h.direct) {
+    IRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(item_hist_direct_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                static_cast<int>(HIST_DIRECT_MAX * sizeof(uint32_t))));
+    hipLaunchKernelGGL(item_hist_direct_kernel, dim3(static_cast<unsigned>(h.grid)), dim3(1024),
+                       static_cast<size_t>(n_items) * sizeof(uint32_t), s, rec, n, static_cast<int32_t>(n_items), item_cnt);
+  } else {
+    hipLaunchKernelGGL(item_hist_kernel, dim3(static_cast<unsigned>(h.grid)), dim3(1024), 0, s, rec, n, item_cnt);
+  }
+}
+
+// EvalParams of a ranking against the evaluator's ground truth (retrieve = 0): rows [offset, offset + rows) of the
+// evaluator, lists into e->rec_out, per-user terms into e->row_out (both sized here)
+EvalParams metric_params(irs_evaluator *e, const void *scores, int64_t rows, int64_t cutoff, int64_t offset, bool rwc) {
   e->row_out.alloc(rows);
   e->rec_out.alloc(rows * cutoff);
   e->todo.alloc(rows);
-  EvalParams p;
-  p.scores = d_scores;
+  EvalParams p{};
+  p.scores = scores;
   p.rows = rows;
   p.n_items = e->n_items;
   p.offset = offset;
@@ -1322,6 +216,16 @@ void rank_block(irs_evaluator *e, const void *d_scores, int64_t rows, int64_t cu
   p.out = e->row_out.ptr;
   p.rec_out = e->rec_out.ptr;
   p.item_cnt = e->item_cnt.ptr;
+  return p;
+}
+
+// ranks `rows` rows already resident at `d_scores` and accumulates into out / item_cnt
+// (`running`, when given: the per-user terms are added to `running` in HOST_LOOP_ROWS-row chunks, chunk after
+// chunk, instead of to e->metrics - see CutoffTotals)
+template <class T>
+void rank_block(irs_evaluator *e, const void *d_scores, int64_t rows, int64_t cutoff,
+                int64_t offset, bool rwc, hipStream_t s, irs_metrics *running = nullptr) {
+  const EvalParams p = metric_params(e, d_scores, rows, cutoff, offset, rwc);
   launch_rank<T>(p, e->n_items, s, e->todo.ptr);
   launch_item_hist(e->rec_out.ptr, rows * cutoff, e->item_cnt.ptr, s, e->n_items);
   if (running) {
@@ -1338,23 +242,6 @@ void rank_block(irs_evaluator *e, const void *d_scores, int64_t rows, int64_t cu
   IRS_HIP(hipGetLastError());
 }
 
-// Metrics::merge (evaluator.cpp:76-85: plain sums) on the device, one thread, and the item histogram beside it:
-// a call that walks its users in blocks folds each block's result here instead of reading it back
-__global__ void metrics_fold_kernel(const irs_metrics *__restrict__ part, irs_metrics *__restrict__ into) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  into->valid_user += part->valid_user;
-  into->total_user += part->total_user;
-  into->hit += part->hit;
-  into->recall += part->recall;
-  into->ndcg += part->ndcg;
-  into->precision += part->precision;
-  into->map += part->map;
-}
-__global__ void counts_fold_kernel(const unsigned long long *__restrict__ part, int64_t n,
-                                   unsigned long long *__restrict__ into) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i < n) into[i] += part[i];
-}
 
 void begin_accumulate(irs_evaluator *e, hipStream_t s) {
   e->metrics.alloc(1);
@@ -1513,13 +400,17 @@ EvalParams retrieve_params(const void *scores, int64_t rows, int64_t n_items, in
   return p;
 }
 
-bool ensure_mask_bitmap(irs_evaluator *e, int64_t rows, int64_t words, const int64_t *d_mptr,
-                        const int32_t *d_midx, hipStream_t s, bool cacheable = true);
-
-// IRSPACK_AMD_EVAL_EMIT=0 switches the threshold-filtered path off (A/B against the two-pass one).
-bool emit_enabled() {
-  const char *e = std::getenv("IRSPACK_AMD_EVAL_EMIT");
+// The switches of the fused call, on unless set to 0 (read per call: tests toggle them):
+//   IRSPACK_AMD_EVAL_EMIT          the threshold-filtered path (off: A/B against the two-pass one)
+//   IRSPACK_AMD_EVAL_BOUND         its norm-bound pruning (off: the emit path scores every tile)
+//   IRSPACK_AMD_EVAL_SAMPLE_FUSED  its sample pass in one launch (off: three launches per 32,768 users, round 5)
+bool env_on(const char *name) {
+  const char *e = std::getenv(name);
   return e ? std::atoi(e) != 0 : true;
+}
+EnvInt env_int(const char *name) {
+  const char *v = std::getenv(name);
+  return EnvInt{v != nullptr, v ? std::atoll(v) : 0};
 }
 
 int device_cu_count(int device) {
@@ -1534,22 +425,10 @@ int device_cu_count(int device) {
   return n;
 }
 
-// IRSPACK_AMD_EVAL_SAMPLE_FUSED=0: the sample pass as three launches per 32,768 users (round 5).
-bool sample_fused_enabled() {
-  const char *e = std::getenv("IRSPACK_AMD_EVAL_SAMPLE_FUSED");
-  return e ? std::atoi(e) != 0 : true;
-}
-
-// IRSPACK_AMD_EVAL_BOUND=0: the emit path scores every tile (no norm-bound pruning).
-bool bound_enabled() {
-  const char *e = std::getenv("IRSPACK_AMD_EVAL_BOUND");
-  return e ? std::atoi(e) != 0 : true;
-}
-
 // Builds (or reuses) the bitmap + per-row count of the mask CSR; false when it would not fit.
 bool ensure_mask_bitmap(irs_evaluator *e, int64_t rows, int64_t words, const int64_t *d_mptr,
                         const int32_t *d_midx, hipStream_t s, bool cacheable) {
-  if (static_cast<double>(rows) * words * 8.0 > 2147483648.0) return false;
+  if (!mask_bitmap_fits(rows, words)) return false;
   const bool cached = cacheable && d_mptr == e->mask_ptr.ptr && e->mask_bits_rows == rows;
   if (!cached) {
     e->mask_bits.alloc(static_cast<size_t>(rows) * words);
@@ -1573,359 +452,346 @@ bool ensure_mask_bitmap(irs_evaluator *e, int64_t rows, int64_t words, const int
   return true;
 }
 
-// The threshold-filtered path of irs_eval_get_metrics_ials (eval_fused_kernels.hpp, second
-// half).  Returns false when the call is outside its domain or had to be abandoned; the caller
-// then runs the two-pass path.
-// One pass of the path over the users [begin, begin + rows): `first` = the first pass of a call
-// (it prepares the item side: norms, order, sample rows), `single` = the only one (the mask
-// bitmap of a resident mask may then be kept for the next call).
+// ---- The threshold-filtered path of irs_eval_get_metrics_ials (eval_fused_kernels.hpp, second half). ----
+// One pass of it over the users [begin, begin + rows): what the stages below share.  `plan` (eval_emit_plan.hpp)
+// holds every decision; the stages launch, in this order, on the one stream.
+struct EmitPass {
+  irs_evaluator *e;
+  irs_ials_trainer *t;
+  hipStream_t s;
+  EmitPlan plan;
+  const float *user, *item;  // the trainer's factor tables, [*, KP]
+  int32_t KP, dev;
+  int64_t ni;
+  int64_t begin, rows, cutoff, offset;
+  bool rwc, first;           // first: the first pass of a call prepares the item side
+  const int64_t *d_mptr;     // mask CSR of the pass's rows, or null
+  const int32_t *d_midx;
+  float norm_c;              // rounding allowance of the norms
+};
+// e->bad_flag: [0] flags, [1] hard rows at the end, [2] hard rows after the sample pass, [3] workgroups
+// ([4..5]: the scored-tile count, 64 bits - one block, so that the call's single read-back is ONE copy, into
+// page-locked memory: two pageable copies and their staging cost ~50 us of a 1.2 ms call)
+enum { FLAG_BAD = 0, FLAG_HARD = 1, FLAG_HARD_SAMPLE = 2, FLAG_WG = 3, FLAG_TILES = 4, FLAG_WORDS = 8 };
+
+void scores_prefix(const EmitPass &c, int64_t r0, int64_t r1, int64_t n_prefix, const float *item_rows,
+                   const float *user_rows, float *out) {
+  if (irs_ials_scores_prefix_device_(c.t, r0, r1, n_prefix, item_rows, user_rows, out) != IRS_OK)
+    throw std::runtime_error(irs_last_error());
+}
+
+// 1. item side (bounded variant): items in order of decreasing norm - the sample is then the items of largest
+//    norm, which hold most of every user's final list.  iota covers the items' sort and this pass's users'.
+void emit_item_side(const EmitPass &c) {
+  irs_evaluator *e = c.e;
+  const int64_t ni = c.ni, n_iota = std::max(ni, c.rows);
+  e->iota.alloc(n_iota);
+  hipLaunchKernelGGL(iota_kernel, dim3(ceil_div(n_iota, 256)), dim3(256), 0, c.s, e->iota.ptr, n_iota);
+  if (!c.first) return;  // (the item side is ready)
+  e->inorm.alloc(ni);
+  e->inorm_sorted.alloc(ni);
+  e->iperm.alloc(ni);
+  e->iinv.alloc(ni);
+  hipLaunchKernelGGL(row_norm_up_kernel, dim3(ceil_div(ni, 16)), dim3(256), 0, c.s, c.item, int64_t(0),
+                     ni, c.KP, c.norm_c, e->inorm.ptr, e->bad_flag.ptr);
+  sort_pairs_f32(true, e->inorm.ptr, e->inorm_sorted.ptr, e->iota.ptr, e->iperm.ptr, ni, e->sort_tmp, c.s);
+  hipLaunchKernelGGL(inverse_perm_kernel, dim3(ceil_div(ni, 256)), dim3(256), 0, c.s, e->iperm.ptr, ni,
+                     e->iinv.ptr);
+  e->sample_item.alloc(static_cast<size_t>(EM_SAMPLE2) * c.KP);
+  hipLaunchKernelGGL(gather_rows_kernel, dim3(ceil_div(int64_t(EM_SAMPLE2) * (c.KP / 4), 256)), dim3(256),
+                     0, c.s, c.item, e->iperm.ptr, static_cast<int64_t>(EM_SAMPLE2), c.KP,
+                     e->sample_item.ptr, static_cast<const int32_t *>(nullptr));
+}
+
+// 2. sample pass: thresholds from the first n_sample items - in one launch, or in blocks of users
+void emit_sample_tau(const EmitPass &c) {
+  irs_evaluator *e = c.e;
+  const EmitPlan &pl = c.plan;
+  const int64_t rows = c.rows, n_sample = pl.n_sample;
+  e->tau.alloc(rows);
+  e->fused_scores.alloc(std::max(static_cast<size_t>(std::min(pl.sample_block, rows)) * n_sample,
+                                 static_cast<size_t>(pl.hcap) * EM_SAMPLE2));
+  if (pl.fused_sample) {
+    SampleParams sp{};
+    sp.user = c.user;
+    sp.sample = e->sample_item.ptr;
+    sp.begin = c.begin;
+    sp.rows = rows;
+    sp.mask_ptr = c.d_mptr;
+    sp.mask_idx = c.d_midx;
+    sp.iinv = e->iinv.ptr;
+    sp.cutoff = static_cast<int32_t>(c.cutoff);
+    sp.tau = e->tau.ptr;
+    sp.hard = e->hard.ptr;
+    sp.bad_flag = e->bad_flag.ptr;
+    auto launch = [&](auto kernel) {
+      IRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(SF_LDS_BYTES)));
+      const int64_t grid = sample_fused_grid(rows, pl.sample_per_cu, device_cu_count(c.dev));
+      hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(grid)), dim3(512), SF_LDS_BYTES, c.s, sp);
+    };
+    switch (c.KP) {
+      case 16: launch(sample_tau_fused_kernel<16>); break;
+      case 32: launch(sample_tau_fused_kernel<32>); break;
+      case 64: launch(sample_tau_fused_kernel<64>); break;
+      default: launch(sample_tau_fused_kernel<128>); break;
+    }
+    return;
+  }
+  const int32_t *no_list = nullptr;
+  for (int64_t b = 0; b < rows; b += pl.sample_block) {
+    const int64_t m = std::min(pl.sample_block, rows - b);
+    scores_prefix(c, c.begin + b, c.begin + b + m, n_sample, pl.bounded ? e->sample_item.ptr : nullptr, nullptr,
+                  e->fused_scores.ptr);
+    if (c.d_mptr && pl.bounded) {
+      const int64_t q0 = e->mask_ptr_host[b], q1 = e->mask_ptr_host[b + m];
+      if (q1 > q0)
+        hipLaunchKernelGGL(mask_entries_perm_kernel, dim3(ceil_div(q1 - q0, 256)), dim3(256), 0, c.s,
+                           e->fused_scores.ptr, n_sample, b, q0, q1, e->mask_row.ptr, c.d_midx,
+                           e->iinv.ptr);
+    } else if (c.d_mptr)
+      hipLaunchKernelGGL(mask_rows_kernel, dim3(m), dim3(64), 0, c.s, e->fused_scores.ptr, m,
+                         n_sample, c.d_mptr + b, c.d_midx);
+    hipLaunchKernelGGL((sample_tau_kernel<8>), dim3(static_cast<unsigned>(ceil_div(m, 4))), dim3(256),
+                       0, c.s, e->fused_scores.ptr, m, n_sample,
+                       static_cast<int32_t>(c.cutoff), e->tau.ptr + b, e->bad_flag.ptr,
+                       e->hard.ptr + b, no_list, no_list);
+  }
+}
+
+// 3. second chance: up to hcap hard rows against the EM_SAMPLE2 items of largest norm (no host round trip: the
+//    kernels run on hcap rows and stop at the device-side count)
+void emit_second_chance(const EmitPass &c) {
+  irs_evaluator *e = c.e;
+  const int64_t HCAP = c.plan.hcap;
+  const int32_t *n_hard1 = e->bad_flag.ptr + FLAG_HARD_SAMPLE;
+  hipLaunchKernelGGL(collect_hard_kernel, dim3(ceil_div(c.rows, 256)), dim3(256), 0, c.s, e->hard.ptr,
+                     e->gt_ptr.ptr, c.offset, c.rows, e->hard_list.ptr, e->bad_flag.ptr + FLAG_HARD_SAMPLE,
+                     static_cast<int32_t>(HCAP));
+  e->hard_user.alloc(static_cast<size_t>(HCAP) * c.KP);
+  hipLaunchKernelGGL(gather_rows_kernel, dim3(ceil_div(HCAP * (c.KP / 4), 256)), dim3(256), 0, c.s,
+                     c.user + c.begin * c.KP, e->hard_list.ptr, HCAP, c.KP, e->hard_user.ptr, n_hard1);
+  scores_prefix(c, 0, HCAP, EM_SAMPLE2, e->sample_item.ptr, e->hard_user.ptr, e->fused_scores.ptr);
+  const int32_t *list = e->hard_list.ptr;
+  if (c.d_mptr)
+    hipLaunchKernelGGL(mask_rows_perm_kernel, dim3(HCAP), dim3(64), 0, c.s, e->fused_scores.ptr, HCAP,
+                       static_cast<int64_t>(EM_SAMPLE2), c.d_mptr, c.d_midx, e->iinv.ptr, list, n_hard1);
+  hipLaunchKernelGGL((sample_tau_kernel<8>), dim3(static_cast<unsigned>(ceil_div(HCAP, 4))), dim3(256),
+                     0, c.s, e->fused_scores.ptr, HCAP, static_cast<int64_t>(EM_SAMPLE2),
+                     static_cast<int32_t>(c.cutoff), e->tau.ptr, e->bad_flag.ptr, e->hard.ptr, list, n_hard1);
+}
+
+// 4. (bounded variant) users in order of increasing pruning radius, what each 64-user tile still needs, and the
+//    work list: only workgroups with a live tile are launched (the others would still queue for a workgroup slot
+//    and its LDS just to leave).  Returns the grid of score_emit_kernel.
+int32_t emit_work_list(const EmitPass &c, EmitParams &f) {
+  irs_evaluator *e = c.e;
+  const EmitPlan &pl = c.plan;
+  const int64_t rows = c.rows, n_ut = pl.n_ut;
+  unsigned long long *const tiles_scored_dev = reinterpret_cast<unsigned long long *>(e->bad_flag.ptr + FLAG_TILES);
+  e->unorm.alloc(rows);
+  e->radius.alloc(rows);
+  e->radius_sorted.alloc(rows);
+  e->uperm.alloc(rows);
+  e->limit_tiles.alloc(n_ut);
+  hipLaunchKernelGGL(row_norm_up_kernel, dim3(ceil_div(rows, 16)), dim3(256), 0, c.s, c.user, c.begin, rows,
+                     c.KP, c.norm_c, e->unorm.ptr, e->bad_flag.ptr);
+  hipLaunchKernelGGL(prune_radius_kernel, dim3(ceil_div(rows, 256)), dim3(256), 0, c.s, e->tau.ptr,
+                     e->unorm.ptr, e->gt_ptr.ptr, c.offset, rows, e->hard.ptr, e->radius.ptr);
+  sort_pairs_f32(false, e->radius.ptr, e->radius_sorted.ptr, e->iota.ptr, e->uperm.ptr, rows, e->sort_tmp, c.s);
+  hipLaunchKernelGGL(tile_limit_kernel, dim3(ceil_div(n_ut, 256)), dim3(256), 0, c.s,
+                     e->radius_sorted.ptr, rows, e->inorm_sorted.ptr, c.ni, e->limit_tiles.ptr,
+                     tiles_scored_dev);
+  f.iperm = e->iperm.ptr;
+  f.uperm = e->uperm.ptr;
+  f.limit_tiles = e->limit_tiles.ptr;
+  e->wg_prefix.alloc(n_ut + 1);
+  hipLaunchKernelGGL(wg_scan_kernel, dim3(1), dim3(1024), 0, c.s, e->limit_tiles.ptr, n_ut,
+                     e->wg_prefix.ptr, e->bad_flag.ptr + FLAG_WG);
+  int32_t n_wg = 0;
+  if (pl.wg_len_on_device) {
+    n_wg = pl.wg_grid;
+    e->wg_desc.alloc(std::max<int64_t>(pl.wg_bound, 1));
+    f.n_wg = e->bad_flag.ptr + FLAG_WG;
+  } else {  // the length comes back first
+    IRS_HIP(hipMemcpyAsync(&n_wg, e->bad_flag.ptr + FLAG_WG, sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+    IRS_HIP(hipStreamSynchronize(c.s));
+    e->wg_desc.alloc(std::max<int64_t>(n_wg, 1));
+  }
+  hipLaunchKernelGGL(wg_fill_kernel, dim3(ceil_div(n_ut, 4)), dim3(256), 0, c.s, e->wg_prefix.ptr,
+                     e->limit_tiles.ptr, n_ut, e->wg_desc.ptr);
+  f.wg_desc = e->wg_desc.ptr;
+  return n_wg;
+}
+
+// 5. the whole score matrix, candidates only: `tiles` 64 x 64 tiles, four per workgroup
+void emit_scores(const EmitPass &c, const EmitParams &f, int64_t tiles) {
+  const size_t lds = 4 * 64 * FZ_SROW * sizeof(float) + 4 * 64 * sizeof(int32_t);
+  auto launch = [&](auto kernel) {
+    IRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(ceil_div(tiles, 4))), dim3(256), lds, c.s, f);
+  };
+#define IRS_EMIT_CASE(KK)                                        \
+  case KK:                                                       \
+    if (c.plan.bounded) launch(score_emit_kernel<KK, true>);     \
+    else launch(score_emit_kernel<KK, false>);                   \
+    break;
+  switch (c.KP) {  // (emit_width_ok: one of these)
+    IRS_EMIT_CASE(16)
+    IRS_EMIT_CASE(32)
+    IRS_EMIT_CASE(64)
+    IRS_EMIT_CASE(128)
+    IRS_EMIT_CASE(192)
+    IRS_EMIT_CASE(256)
+    default: break;
+  }
+#undef IRS_EMIT_CASE
+}
+
+// 6. rank the candidates, metrics; the rows left hard are listed and counted
+EvalParams emit_rank_candidates(const EmitPass &c, const EmitParams &f, const int32_t *n_masked) {
+  irs_evaluator *e = c.e;
+  EvalParams p = metric_params(e, nullptr, c.rows, c.cutoff, c.offset, c.rwc);
+  p.todo = e->todo.ptr;
+  const dim3 grid(static_cast<unsigned>(ceil_div(c.rows, 4)));
+  hipLaunchKernelGGL((rank_cand_kernel<8>), grid, dim3(256), 0, c.s, p, f, n_masked);
+  hipLaunchKernelGGL(rank_cand_slow_kernel, grid, dim3(256), 0, c.s, p, f, n_masked);
+  hipLaunchKernelGGL(collect_hard_kernel, dim3(ceil_div(c.rows, 256)), dim3(256), 0, c.s, e->hard.ptr,
+                     e->gt_ptr.ptr, c.offset, c.rows, e->hard_list.ptr, e->bad_flag.ptr + FLAG_HARD,
+                     static_cast<int32_t>(c.rows));
+  IRS_HIP(hipGetLastError());
+  return p;
+}
+
+// 7. the hard rows from their full score rows, in chunks: gather the user factors -> scores -> mask -> the general
+//    ranking (no `todo` scratch; why: emit_abandon), all through the row list
+void emit_hard_rows(const EmitPass &c, const EvalParams &p, int64_t n_hard) {
+  irs_evaluator *e = c.e;
+  const int64_t ni = c.ni, chunk = hard_row_chunk(n_hard, ni);
+  e->hard_user.alloc(static_cast<size_t>(chunk) * c.KP);
+  e->fused_scores.alloc(static_cast<size_t>(chunk) * ni);
+  for (int64_t b = 0; b < n_hard; b += chunk) {
+    const int64_t m = std::min(chunk, n_hard - b);
+    const int32_t *list = e->hard_list.ptr + b;
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(ceil_div(m * (c.KP / 4), 256)), dim3(256), 0, c.s,
+                       c.user + c.begin * c.KP, list, m, c.KP, e->hard_user.ptr,
+                       static_cast<const int32_t *>(nullptr));
+    scores_prefix(c, 0, m, ni, nullptr, e->hard_user.ptr, e->fused_scores.ptr);
+    if (c.d_mptr)
+      hipLaunchKernelGGL(mask_rows_kernel, dim3(m), dim3(256), 0, c.s, e->fused_scores.ptr, m, ni, c.d_mptr,
+                         c.d_midx, list);
+    EvalParams q = p;
+    q.scores = e->fused_scores.ptr;
+    q.rows = m;
+    q.row_map = list;
+    launch_rank<float>(q, ni, c.s, nullptr);
+  }
+  IRS_HIP(hipGetLastError());
+}
+
+// 8. item histogram of the lists, sum of the per-user terms (one level, or chunks and then the chunks in order)
+void emit_hist_reduce(const EmitPass &c) {
+  irs_evaluator *e = c.e;
+  const int64_t rows = c.rows;
+  launch_item_hist(e->rec_out.ptr, rows * c.cutoff, e->item_cnt.ptr, c.s, e->n_items);
+  if (c.plan.two_level) {
+    const int64_t chunk = c.plan.reduce_chunk;
+    const int nb = static_cast<int>(ceil_div(rows, chunk));
+    e->row_partials.alloc(nb);
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(nb), dim3(1024), 0, c.s, e->row_out.ptr, rows,
+                       e->metrics.ptr, e->row_partials.ptr, chunk);
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(64), 0, c.s, e->row_partials.ptr, nb, rows,
+                       e->metrics.ptr);
+  } else {
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(1024), 0, c.s, e->row_out.ptr, rows,
+                       e->metrics.ptr, static_cast<RowPartial *>(nullptr), int64_t(0));
+  }
+  IRS_HIP(hipGetLastError());
+}
+
+// One pass.  Returns false when the call is outside the path's domain or had to be abandoned; the caller then
+// runs the two-pass path.  `single` = the only pass of the call (the mask bitmap of a resident mask may then be
+// kept for the next call).
 bool emit_block(irs_evaluator *e, irs_ials_trainer *t, int64_t begin, int64_t rows,
                 const int64_t *d_mptr, const int32_t *d_midx, int64_t cutoff, int64_t offset,
                 bool rwc, hipStream_t s, bool first, bool single) {
-  if (!emit_enabled() || e->rec_mode != 0 || cutoff > FZ_MAX_CUTOFF || rows <= 0) return false;
-  const float *user = nullptr, *item = nullptr;
-  int32_t KP = 0, dev = 0;
-  int64_t nu = 0, ni = 0;
+  EmitFacts facts{env_on("IRSPACK_AMD_EVAL_EMIT"), env_on("IRSPACK_AMD_EVAL_BOUND"),
+                  env_on("IRSPACK_AMD_EVAL_SAMPLE_FUSED"), env_int("IRSPACK_AMD_EVAL_SAMPLE"),
+                  e->rec_mode, cutoff, rows, 0, 0, e->n_items};
+  if (!emit_call_in_domain(facts)) return false;
+  EmitPass c{e, t, s, EmitPlan{}, nullptr, nullptr, 0, 0, 0, begin, rows, cutoff, offset, rwc, first, d_mptr, d_midx, 0.0f};
+  int64_t nu = 0;
   void *sv = nullptr;
-  if (irs_ials_factors_device_(t, &user, &item, &KP, &nu, &ni, &sv, &dev) != IRS_OK)
+  if (irs_ials_factors_device_(t, &c.user, &c.item, &c.KP, &nu, &c.ni, &sv, &c.dev) != IRS_OK)
     throw std::runtime_error(irs_last_error());
-  if (KP > 256) return false;  // K > 256: the two-pass path (run-time-sized scoring kernel)
-  // worth it only when the sample is a small part of the catalogue
-  if (ni != e->n_items || ni < 4 * EM_SAMPLE || rows > (int64_t(1) << 31) / EM_CAP) return false;
-  const bool bounded = bound_enabled() && ni < (int64_t(1) << 31) && rows < (int64_t(1) << 31);
-  // items of the sample pass.  Sorted by norm (bounded variant) a few hundred items already
-  // hold nearly every user's threshold; IRSPACK_AMD_EVAL_SAMPLE overrides (multiples of 64).
-  // The users it leaves without one (they have seen almost all of the sample) get a second
-  // chance on EM_SAMPLE2 items.
-  const int64_t env_sample = [] {  // (read per call: tests toggle it)
-    const char *v = std::getenv("IRSPACK_AMD_EVAL_SAMPLE");
-    return v ? std::max<int64_t>(64, std::atoll(v) / 64 * 64) : int64_t(0);
-  }();
-  const int64_t n_sample = std::min<int64_t>(env_sample ? env_sample : (bounded ? EM_SAMPLE_SORTED : EM_SAMPLE),
-                                             EM_SAMPLE2);
-  const int64_t words = ceil_div(ni, 64);
+  facts.KP = c.KP;
+  facts.ni = c.ni;
+  const EmitPlan &pl = c.plan = plan_emit_pass(facts);
+  if (!pl.ok) return false;
+  c.norm_c = 1.0f + (c.KP + 16) * 2.5e-7f;
   const uint64_t *bits = nullptr;
   const int32_t *n_masked = nullptr;
   if (d_mptr) {
-    if (!ensure_mask_bitmap(e, rows, words, d_mptr, d_midx, s, single)) return false;
+    if (!ensure_mask_bitmap(e, rows, pl.words, d_mptr, d_midx, s, single)) return false;
     bits = e->mask_bits.ptr;
     n_masked = e->mask_count.ptr;
   }
-  // [0] flags, [1] hard rows at the end, [2] hard rows after the sample pass, [3] workgroups
-  // ([4..5]: the scored-tile count, 64 bits - one block, so that the call's single read-back is ONE copy, into
-  // page-locked memory: two pageable copies and their staging cost ~50 us of a 1.2 ms call)
-  e->bad_flag.alloc(8);
-  IRS_HIP(hipMemsetAsync(e->bad_flag.ptr, 0, 8 * sizeof(int32_t), s));
-  unsigned long long *const tiles_scored_dev = reinterpret_cast<unsigned long long *>(e->bad_flag.ptr + 4);
-  if (!e->flags_host) IRS_HIP(hipHostMalloc(reinterpret_cast<void **>(&e->flags_host), 8 * sizeof(int32_t), hipHostMallocDefault));
+  e->bad_flag.alloc(FLAG_WORDS);
+  IRS_HIP(hipMemsetAsync(e->bad_flag.ptr, 0, FLAG_WORDS * sizeof(int32_t), s));
+  if (!e->flags_host)
+    IRS_HIP(hipHostMalloc(reinterpret_cast<void **>(&e->flags_host), FLAG_WORDS * sizeof(int32_t), hipHostMallocDefault));
   e->hard.alloc(rows);
   e->hard_list.alloc(rows);
   IRS_HIP(hipMemsetAsync(e->hard.ptr, 0, rows * sizeof(int32_t), s));
-  // ---- 0. bounded variant: items in order of decreasing norm (the sample is then the items
-  //         of largest norm, which hold most of every user's final list)
-  const float norm_c = 1.0f + (KP + 16) * 2.5e-7f;
-  if (bounded && !first) {  // (the item side is ready; iota must still cover this pass's rows)
-    e->iota.alloc(std::max(ni, rows));
-    hipLaunchKernelGGL(iota_kernel, dim3(ceil_div(std::max(ni, rows), 256)), dim3(256), 0, s,
-                       e->iota.ptr, std::max(ni, rows));
-  }
-  if (bounded && first) {
-    e->iota.alloc(std::max(ni, rows));
-    hipLaunchKernelGGL(iota_kernel, dim3(ceil_div(std::max(ni, rows), 256)), dim3(256), 0, s,
-                       e->iota.ptr, std::max(ni, rows));
-    e->inorm.alloc(ni);
-    e->inorm_sorted.alloc(ni);
-    e->iperm.alloc(ni);
-    e->iinv.alloc(ni);
-    hipLaunchKernelGGL(row_norm_up_kernel, dim3(ceil_div(ni, 16)), dim3(256), 0, s, item, int64_t(0),
-                       ni, KP, norm_c, e->inorm.ptr, e->bad_flag.ptr);
-    sort_pairs_f32(true, e->inorm.ptr, e->inorm_sorted.ptr, e->iota.ptr, e->iperm.ptr, ni,
-                   e->sort_tmp, s);
-    hipLaunchKernelGGL(inverse_perm_kernel, dim3(ceil_div(ni, 256)), dim3(256), 0, s, e->iperm.ptr, ni,
-                       e->iinv.ptr);
-    e->sample_item.alloc(static_cast<size_t>(EM_SAMPLE2) * KP);
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(ceil_div(int64_t(EM_SAMPLE2) * (KP / 4), 256)), dim3(256),
-                       0, s, item, e->iperm.ptr, static_cast<int64_t>(EM_SAMPLE2), KP,
-                       e->sample_item.ptr, static_cast<const int32_t *>(nullptr));
-  }
-  // ---- 1. sample pass: thresholds from the first n_sample items, in blocks of users
-  e->tau.alloc(rows);
-  {
-    const int64_t SB = 32768;  // users per sample block (<= 256 MB of scores)
-    const int64_t HCAP = std::min<int64_t>(EM_HARD_CAP, rows);
-    e->fused_scores.alloc(std::max(static_cast<size_t>(std::min(SB, rows)) * n_sample,
-                                   static_cast<size_t>(HCAP) * EM_SAMPLE2));
-    const int32_t *no_list = nullptr;
-    // the whole pass in one launch (sample_tau_fused_kernel); IRSPACK_AMD_EVAL_SAMPLE_FUSED=0: the three
-    // launches per block of users below (A/B)
-    const bool fused_sample = bounded && n_sample == SF_ITEMS && (KP == 16 || KP == 32 || KP == 64 || KP == 128) &&
-                              sample_fused_enabled();
-    if (fused_sample) {
-      SampleParams sp{};
-      sp.user = user;
-      sp.sample = e->sample_item.ptr;
-      sp.begin = begin;
-      sp.rows = rows;
-      sp.mask_ptr = d_mptr;
-      sp.mask_idx = d_midx;
-      sp.iinv = e->iinv.ptr;
-      sp.cutoff = static_cast<int32_t>(cutoff);
-      sp.tau = e->tau.ptr;
-      sp.hard = e->hard.ptr;
-      sp.bad_flag = e->bad_flag.ptr;
-      auto launch = [&](auto kernel, int per_cu) {
-        IRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(SF_LDS_BYTES)));
-        const int64_t grid = std::min<int64_t>(ceil_div(rows, SF_USERS), int64_t(per_cu) * device_cu_count(dev));
-        hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(grid)), dim3(512), SF_LDS_BYTES, s, sp);
-      };
-      switch (KP) {
-        case 16: launch(sample_tau_fused_kernel<16>, 2); break;
-        case 32: launch(sample_tau_fused_kernel<32>, 2); break;
-        case 64: launch(sample_tau_fused_kernel<64>, 2); break;
-        default: launch(sample_tau_fused_kernel<128>, 1); break;
-      }
-    }
-    for (int64_t b = fused_sample ? rows : 0; b < rows; b += SB) {
-      const int64_t m = std::min(SB, rows - b);
-      if (irs_ials_scores_prefix_device_(t, begin + b, begin + b + m, n_sample,
-                                         bounded ? e->sample_item.ptr : nullptr, nullptr,
-                                         e->fused_scores.ptr) != IRS_OK)
-        throw std::runtime_error(irs_last_error());
-      if (d_mptr && bounded) {
-        const int64_t q0 = e->mask_ptr_host[b], q1 = e->mask_ptr_host[b + m];
-        if (q1 > q0)
-          hipLaunchKernelGGL(mask_entries_perm_kernel, dim3(ceil_div(q1 - q0, 256)), dim3(256), 0, s,
-                             e->fused_scores.ptr, n_sample, b, q0, q1, e->mask_row.ptr, d_midx,
-                             e->iinv.ptr);
-      } else if (d_mptr)
-        hipLaunchKernelGGL(mask_rows_kernel, dim3(m), dim3(64), 0, s, e->fused_scores.ptr, m,
-                           n_sample, d_mptr + b, d_midx);
-      hipLaunchKernelGGL((sample_tau_kernel<8>), dim3(static_cast<unsigned>(ceil_div(m, 4))), dim3(256),
-                         0, s, e->fused_scores.ptr, m, n_sample,
-                         static_cast<int32_t>(cutoff), e->tau.ptr + b, e->bad_flag.ptr,
-                         e->hard.ptr + b, no_list, no_list);
-    }
-    if (bounded && n_sample < EM_SAMPLE2) {
-      // second chance: up to HCAP hard rows against the EM_SAMPLE2 items of largest norm (no
-      // host round trip: the kernels run on HCAP rows and stop at the device-side count)
-      int32_t *n_hard1 = e->bad_flag.ptr + 2;
-      hipLaunchKernelGGL(collect_hard_kernel, dim3(ceil_div(rows, 256)), dim3(256), 0, s, e->hard.ptr,
-                         e->gt_ptr.ptr, offset, rows, e->hard_list.ptr, n_hard1,
-                         static_cast<int32_t>(HCAP));
-      e->hard_user.alloc(static_cast<size_t>(HCAP) * KP);
-      hipLaunchKernelGGL(gather_rows_kernel, dim3(ceil_div(HCAP * (KP / 4), 256)), dim3(256), 0, s,
-                         user + begin * KP, e->hard_list.ptr, HCAP, KP, e->hard_user.ptr,
-                         static_cast<const int32_t *>(n_hard1));
-      if (irs_ials_scores_prefix_device_(t, 0, HCAP, EM_SAMPLE2, e->sample_item.ptr, e->hard_user.ptr,
-                                         e->fused_scores.ptr) != IRS_OK)
-        throw std::runtime_error(irs_last_error());
-      if (d_mptr)
-        hipLaunchKernelGGL(mask_rows_perm_kernel, dim3(HCAP), dim3(64), 0, s, e->fused_scores.ptr, HCAP,
-                           static_cast<int64_t>(EM_SAMPLE2), d_mptr, d_midx, e->iinv.ptr,
-                           static_cast<const int32_t *>(e->hard_list.ptr), static_cast<const int32_t *>(n_hard1));
-      hipLaunchKernelGGL((sample_tau_kernel<8>), dim3(static_cast<unsigned>(ceil_div(HCAP, 4))), dim3(256),
-                         0, s, e->fused_scores.ptr, HCAP, static_cast<int64_t>(EM_SAMPLE2),
-                         static_cast<int32_t>(cutoff), e->tau.ptr, e->bad_flag.ptr, e->hard.ptr,
-                         static_cast<const int32_t *>(e->hard_list.ptr), static_cast<const int32_t *>(n_hard1));
-    }
-  }
-  // ---- 2. the whole score matrix, candidates only
+  if (pl.bounded) emit_item_side(c);
+  emit_sample_tau(c);
+  if (pl.second_chance) emit_second_chance(c);
   e->cand_score.alloc(static_cast<size_t>(rows) * EM_CAP);
   e->cand_item.alloc(static_cast<size_t>(rows) * EM_CAP);
   e->cand_cnt.alloc(rows);
   IRS_HIP(hipMemsetAsync(e->cand_cnt.ptr, 0, rows * sizeof(int32_t), s));
-  EmitParams f;
-  f.user = user;
-  f.item = item;
+  EmitParams f{};
+  f.user = c.user;
+  f.item = c.item;
   f.begin = begin;
   f.rows = rows;
-  f.n_items = ni;
+  f.n_items = c.ni;
   f.mask_bits = bits;
-  f.words = words;
+  f.words = pl.words;
   f.tau = e->tau.ptr;
   f.cand_score = e->cand_score.ptr;
   f.cand_item = e->cand_item.ptr;
   f.cand_cnt = e->cand_cnt.ptr;
   f.bad_flag = e->bad_flag.ptr;
-  f.iperm = f.uperm = f.limit_tiles = nullptr;
-  f.wg_desc = nullptr;
-  f.n_wg = nullptr;
   f.hard = e->hard.ptr;
-  int32_t n_wg = 0;
-  if (bounded) {
-    // users in order of increasing pruning radius, and what each 64-user tile still needs
-    e->unorm.alloc(rows);
-    e->radius.alloc(rows);
-    e->radius_sorted.alloc(rows);
-    e->uperm.alloc(rows);
-    e->limit_tiles.alloc(ceil_div(rows, 64));
-    hipLaunchKernelGGL(row_norm_up_kernel, dim3(ceil_div(rows, 16)), dim3(256), 0, s, user, begin, rows,
-                       KP, norm_c, e->unorm.ptr, e->bad_flag.ptr);
-    hipLaunchKernelGGL(prune_radius_kernel, dim3(ceil_div(rows, 256)), dim3(256), 0, s, e->tau.ptr,
-                       e->unorm.ptr, e->gt_ptr.ptr, offset, rows, e->hard.ptr, e->radius.ptr);
-    sort_pairs_f32(false, e->radius.ptr, e->radius_sorted.ptr, e->iota.ptr, e->uperm.ptr, rows,
-                   e->sort_tmp, s);
-    hipLaunchKernelGGL(tile_limit_kernel, dim3(ceil_div(ceil_div(rows, 64), 256)), dim3(256), 0, s,
-                       e->radius_sorted.ptr, rows, e->inorm_sorted.ptr, ni, e->limit_tiles.ptr,
-                       tiles_scored_dev);
-    f.iperm = e->iperm.ptr;
-    f.uperm = e->uperm.ptr;
-    f.limit_tiles = e->limit_tiles.ptr;
-    // the work list: only workgroups with a live tile are launched (the others would still
-    // queue for a workgroup slot and its LDS just to leave); its length comes back to the host
-    const int64_t n_ut = ceil_div(rows, 64);
-    e->wg_prefix.alloc(n_ut + 1);
-    hipLaunchKernelGGL(wg_scan_kernel, dim3(1), dim3(1024), 0, s, e->limit_tiles.ptr, n_ut,
-                       e->wg_prefix.ptr, e->bad_flag.ptr + 3);
-    // at most ceil(item tiles / 4) entries per user tile.  Up to 2^24 entries (64 MB) the list is sized for
-    // that bound and its length stays on the device (score_emit_kernel walks it with a grid stride);
-    // beyond, the length comes back first
-    const int64_t wg_bound = n_ut * ceil_div(ceil_div(ni, 64), 4);
-    if (wg_bound <= (int64_t(1) << 24)) {
-      n_wg = static_cast<int32_t>(std::min<int64_t>(wg_bound, 32768));  // the grid
-      e->wg_desc.alloc(std::max<int64_t>(wg_bound, 1));
-      f.n_wg = e->bad_flag.ptr + 3;
-    } else {
-      IRS_HIP(hipMemcpyAsync(&n_wg, e->bad_flag.ptr + 3, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-      IRS_HIP(hipStreamSynchronize(s));
-      e->wg_desc.alloc(std::max<int64_t>(n_wg, 1));
-    }
-    hipLaunchKernelGGL(wg_fill_kernel, dim3(ceil_div(n_ut, 4)), dim3(256), 0, s, e->wg_prefix.ptr,
-                       e->limit_tiles.ptr, n_ut, e->wg_desc.ptr);
-    f.wg_desc = e->wg_desc.ptr;
-  }
-  if (!bounded || n_wg > 0) {
-    const int64_t tiles = bounded ? int64_t(n_wg) * 4 : ceil_div(rows, 64) * ceil_div(ni, 64);
-    const size_t lds = 4 * 64 * FZ_SROW * sizeof(float) + 4 * 64 * sizeof(int32_t);
-    auto launch = [&](auto kernel) {
-      IRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-      hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(ceil_div(tiles, 4))), dim3(256), lds, s, f);
-    };
-#define IRS_EMIT_CASE(KK)                                        \
-  case KK:                                                       \
-    if (bounded) launch(score_emit_kernel<KK, true>);            \
-    else launch(score_emit_kernel<KK, false>);                   \
-    break;
-    switch (KP) {
-      IRS_EMIT_CASE(16)
-      IRS_EMIT_CASE(32)
-      IRS_EMIT_CASE(64)
-      IRS_EMIT_CASE(128)
-      IRS_EMIT_CASE(192)
-      IRS_EMIT_CASE(256)
-      default: return false;
-    }
-#undef IRS_EMIT_CASE
-  }
-  // ---- 3. rank the candidates, metrics
-  e->row_out.alloc(rows);
-  e->rec_out.alloc(rows * cutoff);
-  e->todo.alloc(rows);
-  EvalParams p;
-  p.scores = nullptr;
-  p.rows = rows;
-  p.n_items = e->n_items;
-  p.offset = offset;
-  p.gt_ptr = e->gt_ptr.ptr;
-  p.gt_idx = e->gt_idx.ptr;
-  p.rec_mode = 0;
-  p.rec_ptr = e->rec_ptr.ptr;
-  p.rec_items = e->rec_items.ptr;
-  p.cutoff = static_cast<int32_t>(cutoff);
-  p.retrieve = 0;
-  p.recall_with_cutoff = rwc ? 1 : 0;
-  p.disc = e->disc.ptr;
-  p.idcg_prefix = e->idcg_prefix.ptr;
-  p.out = e->row_out.ptr;
-  p.rec_out = e->rec_out.ptr;
-  p.item_cnt = e->item_cnt.ptr;
-  p.todo = e->todo.ptr;
-  const dim3 grid(static_cast<unsigned>(ceil_div(rows, 4)));
-  hipLaunchKernelGGL((rank_cand_kernel<8>), grid, dim3(256), 0, s, p, f, n_masked);
-  hipLaunchKernelGGL(rank_cand_slow_kernel, grid, dim3(256), 0, s, p, f, n_masked);
-  hipLaunchKernelGGL(collect_hard_kernel, dim3(ceil_div(rows, 256)), dim3(256), 0, s, e->hard.ptr,
-                     e->gt_ptr.ptr, offset, rows, e->hard_list.ptr, e->bad_flag.ptr + 1,
-                     static_cast<int32_t>(rows));
-  IRS_HIP(hipGetLastError());
-  IRS_HIP(hipMemcpyAsync(e->flags_host, e->bad_flag.ptr, 8 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  const int64_t tiles = pl.bounded ? int64_t(emit_work_list(c, f)) * 4 : pl.tiles_total;
+  if (tiles > 0) emit_scores(c, f, tiles);
+  const EvalParams p = emit_rank_candidates(c, f, n_masked);
+  IRS_HIP(hipMemcpyAsync(e->flags_host, e->bad_flag.ptr, FLAG_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   IRS_HIP(hipStreamSynchronize(s));
-  const int32_t bad[3] = {e->flags_host[0], e->flags_host[1], e->flags_host[2]};
+  const int32_t flags = e->flags_host[FLAG_BAD], n_hard = e->flags_host[FLAG_HARD];
   unsigned long long tiles_scored = 0;
-  std::memcpy(&tiles_scored, e->flags_host + 4, sizeof(tiles_scored));
-  {
-    const int64_t total = ceil_div(rows, 64) * ceil_div(ni, 64);
-    const int64_t scored = bounded ? static_cast<int64_t>(tiles_scored) : total;
-    if (first) e->stats = irs_eval_stats{bounded ? 2 : 1, 0, 0, 0, n_sample};
-    e->stats.hard_rows += bad[1];
-    e->stats.tiles_total += total;
-    e->stats.tiles_scored += scored;
-  }
-  // non-finite scores (the two-pass path defines the order of NaN), or so many hard rows that
-  // one by one is the slower way: the caller runs the two-pass path
-  if (bad[0] || bad[1] > 1024) return false;
-  if (bad[1] > 0) {
-    // the hard rows from their full score rows, in chunks of <= 1 GB of scores: gather the
-    // user factors -> scores -> mask -> the general ranking, all through the row list
-    const int64_t n_hard = bad[1];
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n_hard, (int64_t(1) << 28) / ni));
-    e->hard_user.alloc(static_cast<size_t>(chunk) * KP);
-    e->fused_scores.alloc(static_cast<size_t>(chunk) * ni);
-    for (int64_t b = 0; b < n_hard; b += chunk) {
-      const int64_t m = std::min(chunk, n_hard - b);
-      const int32_t *list = e->hard_list.ptr + b;
-      hipLaunchKernelGGL(gather_rows_kernel, dim3(ceil_div(m * (KP / 4), 256)), dim3(256), 0, s,
-                         user + begin * KP, list, m, KP, e->hard_user.ptr,
-                         static_cast<const int32_t *>(nullptr));
-      if (irs_ials_scores_prefix_device_(t, 0, m, ni, nullptr, e->hard_user.ptr, e->fused_scores.ptr) != IRS_OK)
-        throw std::runtime_error(irs_last_error());
-      if (d_mptr)
-        hipLaunchKernelGGL(mask_rows_kernel, dim3(m), dim3(256), 0, s, e->fused_scores.ptr, m, ni, d_mptr,
-                           d_midx, list);
-      EvalParams q = p;
-      q.scores = e->fused_scores.ptr;
-      q.rows = m;
-      q.row_map = list;
-      // (no `todo` scratch = the general kernel for every row: a few dozen rows leave the one-wave-per-row
-      // kernel latency bound - 51 us for 76 rows of an ML-20M call, the 1024-thread form takes 12)
-      launch_rank<float>(q, ni, s, n_hard >= 2048 ? e->todo.ptr : nullptr);
-    }
-    IRS_HIP(hipGetLastError());
-  }
-  launch_item_hist(e->rec_out.ptr, rows * cutoff, e->item_cnt.ptr, s, e->n_items);
-  if (rows >= 32768) {  // two levels: 4096-row chunks, then the chunks in order
-    const int64_t chunk = 4096;
-    const int nb = static_cast<int>(ceil_div(rows, chunk));
-    e->row_partials.alloc(nb);
-    hipLaunchKernelGGL(reduce_rows_kernel, dim3(nb), dim3(1024), 0, s, e->row_out.ptr, rows,
-                       e->metrics.ptr, e->row_partials.ptr, chunk);
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(64), 0, s, e->row_partials.ptr, nb, rows,
-                       e->metrics.ptr);
-  } else {
-    hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(1024), 0, s, e->row_out.ptr, rows,
-                       e->metrics.ptr, static_cast<RowPartial *>(nullptr), int64_t(0));
-  }
-  IRS_HIP(hipGetLastError());
+  std::memcpy(&tiles_scored, e->flags_host + FLAG_TILES, sizeof(tiles_scored));
+  if (first) e->stats = irs_eval_stats{pl.bounded ? 2 : 1, 0, 0, 0, pl.n_sample};
+  e->stats.hard_rows += n_hard;
+  e->stats.tiles_total += pl.tiles_total;
+  e->stats.tiles_scored += pl.bounded ? static_cast<int64_t>(tiles_scored) : pl.tiles_total;
+  if (emit_abandon(flags, n_hard)) return false;
+  if (n_hard > 0) emit_hard_rows(c, p, n_hard);
+  emit_hist_reduce(c);
   return true;
 }
 
-
-// The threshold-filtered path over all users of a call, in passes that keep the scratch bounded:
-// the candidate lists take 8 KB per user and the mask bitmap n_items / 8 bytes per user (at most
-// 2 GiB per pass), so a call over millions of users or a catalogue of a million items runs as
-// several passes (IRSPACK_AMD_EVAL_PASS_ROWS overrides the pass size).  False: outside the
+// The threshold-filtered path over all users of a call, in passes that keep the scratch bounded
+// (emit_pass_rows; IRSPACK_AMD_EVAL_PASS_ROWS overrides the pass size).  False: outside the
 // path's domain or abandoned - the caller resets the sums and runs the two-pass path.
 bool emit_path(irs_evaluator *e, irs_ials_trainer *t, int64_t begin, int64_t rows,
                const int64_t *d_mptr, const int32_t *d_midx, int64_t cutoff, int64_t offset,
                bool rwc, hipStream_t s) {
   if (rows <= 0) return false;
-  const char *env_v = std::getenv("IRSPACK_AMD_EVAL_PASS_ROWS");
-  const int64_t env_rows = env_v ? std::max<int64_t>(64, std::atoll(env_v) / 64 * 64) : int64_t(0);
-  const int64_t words = ceil_div(std::max<int64_t>(e->n_items, 1), 64);
-  int64_t pass = std::min<int64_t>(524288, (int64_t(1) << 31) / (words * 8) / 64 * 64);
-  if (env_rows) pass = std::min(pass, env_rows);
-  if (pass < 64) return false;
+  const int64_t pass = emit_pass_rows(e->n_items, env_int("IRSPACK_AMD_EVAL_PASS_ROWS"));
+  if (pass == 0) return false;
   if (rows <= pass) return emit_block(e, t, begin, rows, d_mptr, d_midx, cutoff, offset, rwc, s, true, true);
   for (int64_t b = 0; b < rows; b += pass) {
     const int64_t m = std::min(pass, rows - b);

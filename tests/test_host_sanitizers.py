@@ -8,7 +8,9 @@ available on the pool; this covers the code that runs on host threads:
   (> 2^18 values).
 - tests/host/knn_host_prep_main.cpp: the rest of knn_host_prep.hpp, i.e. what a kNN compute call does on the host
   before it launches - entry scan, chunk cuts, the threaded target pass, launch order, variant choice, arena layout.
-- tests/host/eval_host_prep_main.cpp: eval_host_prep.hpp.
+- tests/host/eval_host_prep_main.cpp: eval_host_prep.hpp, and eval_emit_plan.hpp, i.e. what the evaluator decides on the
+  host - the domain and shape of a pass of the threshold-filtered path, the ranking dispatch, the item-histogram
+  table (against the former chains of conditions, both sides of every boundary).
 - tests/host/ials_host_plan_main.cpp: ials_host_plan.hpp, i.e. what the iALS path decides on the host - the task plan
   of a side (chunks, fold groups, the short tail, the row classes) and the route of a half-step (kernel family and
   instance flags, against the former chains of conditions).
@@ -99,18 +101,33 @@ def test_mt19937_jump_ahead_arithmetic(tmp_path, portable):
 _HOST_CXX = shutil.which("g++") or shutil.which("clang++")
 
 
+def _eval_host_prep(tmp_path, flags):
+    exe = str(tmp_path / "eval_host_prep_main")
+    src = os.path.join(ROOT, "tests", "host", "eval_host_prep_main.cpp")
+    subprocess.check_call([_HOST_CXX, "-std=c++17", "-pthread", *flags, src, "-o", exe])
+    return subprocess.run([exe], capture_output=True, text=True, timeout=600)
+
+
 @pytest.mark.skipif(_HOST_CXX is None, reason="needs a host C++ compiler")
 def test_evaluator_host_preparation_under_address_and_ub_sanitizers(tmp_path):
     """irspack_amd/csrc/eval_host_prep.hpp - profile, mask and candidate rows, the launch order, the rows per
-    score block (against the five formulas of the entry points, written out), the scan of a sparse W - in a
-    program of its own (tests/host/eval_host_prep_main.cpp), every report fatal."""
-    exe = str(tmp_path / "eval_host_prep_main")
-    src = os.path.join(ROOT, "tests", "host", "eval_host_prep_main.cpp")
-    subprocess.check_call([_HOST_CXX, "-std=c++17", "-O1", "-g", "-pthread", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", src, "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    score block (against the five formulas of the entry points, written out), the scan of a sparse W - and
+    eval_emit_plan.hpp - the pass plan of the threshold-filtered path, the pass size, the bitmap and abandon rules,
+    the ranking dispatch and the histogram table against the former condition chains - in a program of its own
+    (tests/host/eval_host_prep_main.cpp), every report fatal."""
+    r = _eval_host_prep(tmp_path, ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                                   "-fno-omit-frame-pointer"])
     assert r.returncode == 0, r.stderr[-4000:]
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+    assert "eval_host_prep ok" in r.stdout
+
+
+@pytest.mark.skipif(_HOST_CXX is None, reason="needs a host C++ compiler")
+def test_evaluator_host_preparation_plain_optimised_build(tmp_path):
+    """The same program without a sanitizer at -O3 with the library's -ffp-contract=off: the build in which the
+    plan's integer divisions and the bitmap rule's float64 product run as the library runs them."""
+    r = _eval_host_prep(tmp_path, ["-O3", "-ffp-contract=off"])
+    assert r.returncode == 0, r.stderr[-4000:]
     assert "eval_host_prep ok" in r.stdout
 
 
