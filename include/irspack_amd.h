@@ -701,6 +701,97 @@ irs_status irs_bpr_set_state(irs_bpr *t, const float *U, const float *V, const f
 irs_status irs_bpr_stats(irs_bpr *t, irs_bpr_stats_t *out);
 irs_status irs_bpr_destroy(irs_bpr *t);
 
+/* ------------------------------------------------------------------ Mult-VAE
+ * MultVAERecommender (src/irspack/recommenders/multvae.py; the reference trains with jax / haiku / optax and jax's
+ * generator - the trainer here is this library's own statement of the same model).
+ * With I = n_items, H = enc_hidden, Hd = dec_hidden, L = dim_z the eight float32 tables are, in this order,
+ *   W1 [I, H], b1 [H], W2 [H, 2 L], b2 [2 L], W3 [L, Hd], b3 [Hd], W4 [Hd, I], b4 [I],
+ * each with Adam moments m and v of its shape.  Wherever 8 tables are passed they are an array of 8 pointers in
+ * that order; a state is an array of 24: the tables, their m, their v.  Initial tables (init == NULL): biases 0,
+ * weights truncated normal at +-2 sigma, sigma = 1 / sqrt(fan_in), from the counter-based generator keyed by
+ * (seed, table, index).
+ *
+ * One update on n user rows with raw stored values x (t = updates done before it):
+ *   klc = kl_anneal_goal min(1, t / (anneal_end_epoch n_users / minibatch_size))     (run_epochs; step_batch takes it)
+ *   xn = x / sqrt(sum x^2 + 1e-8) per row; xd = xn keep / (1 - dropout_p), keep in {0, 1} per stored entry
+ *   h1 = tanh(xd W1 + b1); [mu | lv] = h1 W2 + b2; std = exp(lv / 2); z = mu + eps std
+ *   h2 = tanh(z W3 + b3); logit = h2 W4 + b4; lsm = logit - logsumexp(logit) per row
+ *   loss = mean_rows(-sum_i lsm x) + klc mean_rows(sum 0.5 (-lv + std^2 + mu^2 - 1))
+ * then Adam (b1 0.9, b2 0.999, eps 1e-8, bias-corrected, optax's form) with the gradient of loss on every element
+ * of every table.  A user without entries takes part (its KL term, and it counts in n); the last batch of an epoch
+ * is short.  l2_regularizer is stored and has no effect, as in the reference.  The order of an epoch is a seeded
+ * bijection of the users keyed by (seed, epoch); keep is a hash of (seed, update, user, stored position) against
+ * dropout_p, eps a Gaussian keyed by (seed, update, user, component).  Evaluation (encode, score): no dropout,
+ * z = mu.
+ *
+ * The gradient of W1 is summed in 64-bit fixed point (scale 2^s, s from the batch length: stats), so the bytes
+ * do not depend on the order of arrival; a contribution that is not finite or reaches 2^8 in magnitude makes the
+ * call return IRS_RUNTIME_ERROR ("the fit has diverged") and the state is lost.  Every other sum has a fixed
+ * order: two runs give identical bytes.
+ *
+ * create      checks everything and keeps host copies; the device is first used by the first call that computes.
+ *             1 <= enc_hidden, dec_hidden <= 574, dim_z >= 1, 0 <= dropout_p < 1, minibatch_size >= 1,
+ *             learning_rate > 0, kl_anneal_goal >= 0, anneal_end_epoch >= 0.
+ * run_epochs  whole epochs, one synchronisation at the end.
+ * order       users [count] of positions [first, first + count) of an epoch (host only).
+ * noise       for n users at one update: keep (one byte per stored entry, the rows in the order of `users`) and
+ *             eps [n, L], as run_epochs draws them.
+ * step_batch  one update on the caller's rows with the caller's keep / eps (NULL: drawn as
+ *             run_epochs would at the current update count) and klc; nll and kl (may be NULL) receive the two
+ *             means of the loss.  Counts as an update, not as an epoch.
+ * gradients   the 8 gradient tables of the last update.
+ * get_state / set_state   24 tables (entries of get_state may be NULL), the update and the epoch counter.
+ * encode      rows of a CSR matrix of n_items columns -> h2 [rows, Hd] and lse [rows] (either may be NULL), so
+ *             that the log-softmax scores are [h2 | 1] [W4; b4] - lse.
+ * score       the same rows -> log-softmax [rows, I] float32.
+ * IRS_INVALID_ARGUMENT for every argument check (all come before any device work); IRS_RUNTIME_ERROR: no device,
+ * not enough device memory for the [batch, I] block, a diverged fit.  One handle is used by one thread at a time. */
+typedef struct irs_multvae irs_multvae;
+typedef struct {
+  int64_t n_updates;         /* updates done */
+  int64_t epoch;             /* epochs done */
+  int64_t batches_per_epoch; /* ceil(n_users / minibatch_size) */
+  int32_t dh2_slab;          /* items per K-slab of dh2 = g W4^T (partials added in slab order) */
+  int32_t dw4_slab;          /* batch rows per K-slab of d[W4; b4] = [h2 | 1]^T g */
+  int32_t scale_log2;        /* s of the fixed-point scale of a full batch */
+  int32_t reserved;
+  double klc_next;           /* klc of the next update of run_epochs */
+  double klc_last;           /* klc, nll and kl of the last update */
+  double nll_last;
+  double kl_last;
+  double epoch_ms;           /* device time of the last epoch run */
+  double encode_ms;          /* that epoch by phase, collected only with IRSPACK_AMD_MULTVAE_PHASES=1 in the */
+  double dense_ms;           /* environment when the handle is made, else 0: encoder input product; the small */
+  double logit_ms;           /* dense products and the latent kernels; logits; softmax and its gradient; */
+  double softmax_ms;         /* d[W4; b4]; dh2; the fixed-point dW1; Adam */
+  double dw4_ms;
+  double dh2_ms;
+  double dw1_ms;
+  double adam_ms;
+} irs_multvae_stats_t;
+irs_status irs_multvae_create(int64_t n_users, int64_t n_items, const int64_t *indptr, const int32_t *indices,
+                              const float *data, int32_t dim_z, int32_t enc_hidden, int32_t dec_hidden,
+                              float dropout_p, float l2_regularizer, double kl_anneal_goal, int64_t anneal_end_epoch,
+                              int64_t minibatch_size, float learning_rate, uint64_t seed,
+                              const float *const *init /* 8 tables, may be NULL */, int32_t device,
+                              irs_multvae **out);
+irs_status irs_multvae_run_epochs(irs_multvae *t, int64_t n_epochs);
+irs_status irs_multvae_order(irs_multvae *t, int64_t epoch, int64_t first, int64_t count, int32_t *users);
+irs_status irs_multvae_noise(irs_multvae *t, int64_t update, int64_t n, const int32_t *users, uint8_t *keep,
+                             float *eps);
+irs_status irs_multvae_step_batch(irs_multvae *t, int64_t n, const int32_t *users, const uint8_t *keep,
+                                  const float *eps, double klc, double *nll, double *kl);
+irs_status irs_multvae_gradients(irs_multvae *t, float *const *grads /* 8 tables */);
+irs_status irs_multvae_get_state(irs_multvae *t, float *const *tables /* 24 */, int64_t *n_updates, int64_t *epoch);
+irs_status irs_multvae_set_state(irs_multvae *t, const float *const *tables /* 24 */, int64_t n_updates,
+                                 int64_t epoch);
+irs_status irs_multvae_encode(irs_multvae *t, int64_t rows, const int64_t *indptr, const int32_t *indices,
+                              const float *data, float *h2, float *lse);
+irs_status irs_multvae_score(irs_multvae *t, int64_t rows, const int64_t *indptr, const int32_t *indices,
+                             const float *data, float *scores);
+irs_status irs_multvae_stats(irs_multvae *t, irs_multvae_stats_t *out);
+irs_status irs_multvae_destroy(irs_multvae *t);
+
 /* ------------------------------------------------------------------ serving
  * Batch top-k recommendations from a model that stays on the device (the reference's path:
  * utils/id_mapping.py:172-223, 399-453 - get_score_remove_seen on the host, then

@@ -137,6 +137,31 @@ class BprStatsStruct(C.Structure):  # irs_bpr_stats_t
     ]
 
 
+class MultVaeStatsStruct(C.Structure):  # irs_multvae_stats_t
+    _fields_ = [
+        ("n_updates", C.c_int64),
+        ("epoch", C.c_int64),
+        ("batches_per_epoch", C.c_int64),
+        ("dh2_slab", C.c_int32),
+        ("dw4_slab", C.c_int32),
+        ("scale_log2", C.c_int32),
+        ("reserved", C.c_int32),
+        ("klc_next", C.c_double),
+        ("klc_last", C.c_double),
+        ("nll_last", C.c_double),
+        ("kl_last", C.c_double),
+        ("epoch_ms", C.c_double),
+        ("encode_ms", C.c_double),
+        ("dense_ms", C.c_double),
+        ("logit_ms", C.c_double),
+        ("softmax_ms", C.c_double),
+        ("dw4_ms", C.c_double),
+        ("dh2_ms", C.c_double),
+        ("dw1_ms", C.c_double),
+        ("adam_ms", C.c_double),
+    ]
+
+
 ABI_VERSION = 4  # IRS_ABI_VERSION of include/irspack_amd.h
 # IRS_EXCHANGE_* of include/irspack_amd.h: how irs_ials_sharded_step moves the solved rows
 EXCHANGE_MODES = {"auto": 0, "broadcast": 1, "mesh": 2, "peer": 3}
@@ -217,6 +242,18 @@ EXPORTED_SYMBOLS = [
     "irs_bpr_set_state",
     "irs_bpr_stats",
     "irs_bpr_destroy",
+    "irs_multvae_create",
+    "irs_multvae_run_epochs",
+    "irs_multvae_order",
+    "irs_multvae_noise",
+    "irs_multvae_step_batch",
+    "irs_multvae_gradients",
+    "irs_multvae_get_state",
+    "irs_multvae_set_state",
+    "irs_multvae_encode",
+    "irs_multvae_score",
+    "irs_multvae_stats",
+    "irs_multvae_destroy",
     "irs_eval_create",
     "irs_eval_destroy",
     "irs_eval_get_metrics",
@@ -276,6 +313,24 @@ ARGTYPES = {
     "irs_bpr_set_state": [C.c_void_p] + [C.POINTER(C.c_float)] * 6 + [C.c_int64],
     "irs_bpr_stats": [C.c_void_p, C.c_void_p],
     "irs_bpr_destroy": [C.c_void_p],
+    "irs_multvae_create": [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                           C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_double, C.c_int64, C.c_int64,
+                           C.c_float, C.c_uint64, C.POINTER(C.POINTER(C.c_float)), C.c_int32, C.POINTER(C.c_void_p)],
+    "irs_multvae_run_epochs": [C.c_void_p, C.c_int64],
+    "irs_multvae_order": [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32)],
+    "irs_multvae_noise": [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_uint8),
+                          C.POINTER(C.c_float)],
+    "irs_multvae_step_batch": [C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_float),
+                               C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)],
+    "irs_multvae_gradients": [C.c_void_p, C.POINTER(C.POINTER(C.c_float))],
+    "irs_multvae_get_state": [C.c_void_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "irs_multvae_set_state": [C.c_void_p, C.POINTER(C.POINTER(C.c_float)), C.c_int64, C.c_int64],
+    "irs_multvae_encode": [C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                           C.POINTER(C.c_float), C.POINTER(C.c_float)],
+    "irs_multvae_score": [C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                          C.POINTER(C.c_float)],
+    "irs_multvae_stats": [C.c_void_p, C.c_void_p],
+    "irs_multvae_destroy": [C.c_void_p],
     "irs_eval_get_metrics_dense_similarity": [
         C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
         C.POINTER(C.c_double), C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32,
@@ -342,6 +397,15 @@ def check(status: int) -> None:
 
 def ptr(a: np.ndarray, ctype):
     return a.ctypes.data_as(C.POINTER(ctype))
+
+
+def ptr_array(arrays, ctype):
+    """a C array of pointers to the arrays (``None`` stays NULL); the arrays must outlive the call"""
+    out = (C.POINTER(ctype) * len(arrays))()
+    for q, a in enumerate(arrays):
+        if a is not None:
+            out[q] = ptr(a, ctype)
+    return out
 
 
 def device_count() -> int:

@@ -300,9 +300,11 @@ class Evaluator:
     def _factor_operands(self, model: Any) -> Optional[Any]:
         """``(user factors (U, k), item factors (I, k))`` when the model scores as a float32 product of two
         factor tables - ``z @ components_`` of the truncated SVD, ``W @ H`` of NMF, ``[U | 1] @ [V | b]^T`` of a
-        trained BPR model - through its class's own ``get_score_block``; ``None`` for anything else (other dtypes,
+        trained BPR model, ``[h2 | 1 | -lse] @ [W4; b4; 1]`` of a trained Mult-VAE model - through its class's own
+        ``get_score_block``; ``None`` for anything else (other dtypes,
         more factors than the device call takes)."""
         from ..recommenders.bpr import BPRFMRecommender
+        from ..recommenders.multvae import MultVAERecommender
         from ..recommenders.nmf import NMFRecommender
         from ..recommenders.truncsvd import TruncatedSVDRecommender
 
@@ -319,6 +321,10 @@ class Evaluator:
             users, items = getattr(model, "W", None), getattr(model, "H", None)
         elif isinstance(model, BPRFMRecommender):
             if type(model).get_score_block is not BPRFMRecommender.get_score_block or model.trainer is None:
+                return None
+            users, items = model.factor_tables()
+        elif isinstance(model, MultVAERecommender):
+            if type(model).get_score_block is not MultVAERecommender.get_score_block or model.trainer is None:
                 return None
             users, items = model.factor_tables()
         else:

@@ -7,6 +7,7 @@ from .bpr import BPRFMRecommender
 from .dense_slim import DenseSLIMRecommender
 from .edlae import EDLAERecommender
 from .ials import IALSRecommender
+from .multvae import MultVAERecommender
 from .knn import (AsymmetricCosineKNNRecommender, CosineKNNRecommender, JaccardKNNRecommender,
                   P3alphaRecommender, RP3betaRecommender, TverskyIndexKNNRecommender)
 from .nmf import NMFRecommender
@@ -21,4 +22,5 @@ __all__ = ["BaseRecommender", "BaseSimilarityRecommender", "IALSRecommender",
            "BaseUserSimilarityRecommender", "CosineUserKNNRecommender",
            "AsymmetricCosineUserKNNRecommender", "SLIMRecommender", "DenseSLIMRecommender",
            "EDLAERecommender", "TruncatedSVDRecommender", "NMFRecommender",
-           "BaseRecommenderWithEarlyStopping", "BPRFMRecommender", "TopPopRecommender"]
+           "BaseRecommenderWithEarlyStopping", "BPRFMRecommender", "TopPopRecommender",
+           "MultVAERecommender"]

@@ -43,6 +43,7 @@ def model_operands(model: Any) -> Optional[Tuple[str, Tuple[Any, ...]]]:
     from .recommenders.base import BaseSimilarityRecommender, BaseUserSimilarityRecommender
     from .recommenders.bpr import BPRFMRecommender
     from .recommenders.ials import IALSRecommender
+    from .recommenders.multvae import MultVAERecommender
     from .recommenders.nmf import NMFRecommender
     from .recommenders.truncsvd import TruncatedSVDRecommender
 
@@ -67,8 +68,13 @@ def model_operands(model: Any) -> Optional[Tuple[str, Tuple[Any, ...]]]:
                 X.dtype != np.float64 or U.shape != (model.n_users, model.n_users):
             return None
         return "user_similarity", (U, X)
-    if isinstance(model, (TruncatedSVDRecommender, NMFRecommender, BPRFMRecommender)):
-        if isinstance(model, BPRFMRecommender):
+    if isinstance(model, (TruncatedSVDRecommender, NMFRecommender, BPRFMRecommender, MultVAERecommender)):
+        if isinstance(model, MultVAERecommender):
+            # [h2 | 1 | -lse] and [W4; b4; 1]: Hd + 2 columns, held by the model per trained state
+            if own is not MultVAERecommender.get_score_block or model.trainer is None:
+                return None
+            users, items = model.factor_tables()
+        elif isinstance(model, BPRFMRecommender):
             # [U | 1] and [V | b]^T: K + 1 columns, held by the model per trained state (a model that is trained
             # further hands out new tables, so both count as new operands)
             if own is not BPRFMRecommender.get_score_block or model.trainer is None:
@@ -216,8 +222,8 @@ class DeviceRecommender:
         found = model_operands(model)
         if found is None:
             raise TypeError(f"{type(model).__name__} is not a model the device can serve: sparse or dense "
-                            "similarity weights, truncated SVD, NMF or a trained iALS or BPR recommender, scoring through "
-                            "its class's own get_score_block.")
+                            "similarity weights, truncated SVD, NMF or a trained iALS, BPR or Mult-VAE recommender, "
+                            "scoring through its class's own get_score_block.")
         self.kind, operands = found
         self._model = weakref.ref(model) if weak_model else (lambda: model)
         self._model_name = type(model).__name__
@@ -400,6 +406,8 @@ class DeviceRecommender:
             F = self.model.compute_user_embedding(Xc)
         elif hasattr(self.model, "decomposer_"):
             F = self.model.decomposer.transform(Xc)  # X @ components_.T
+        elif hasattr(self.model, "profile_factors"):
+            F = self.model.profile_factors(Xc)  # Mult-VAE: [h2 | 1 | -lse] of the rows' own forward pass
         else:
             F = self.model.nmf_model.transform(Xc)  # nmf_transform
         return self._call_factors(F, excl, lists, cutoff)
