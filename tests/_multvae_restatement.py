@@ -88,6 +88,7 @@ def gradients(state, x, keep, eps, dropout_p, klc, dtype=np.float64):
     grads["W2"], grads["b2"] = f["h1"].T @ dml, dml.sum(axis=0, dtype=dtype)
     da1 = (dml @ p["W2"].T) * (dtype(1) - f["h1"] * f["h1"])
     grads["W1"], grads["b1"] = f["xd"].T @ da1, da1.sum(axis=0, dtype=dtype)
+    f["da1"] = da1
     return {k: np.asarray(v, dtype=dtype) for k, v in grads.items()}, f
 
 

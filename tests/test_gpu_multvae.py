@@ -1,22 +1,23 @@
 """MultVAERecommender on the device: single updates and runs of updates against the numpy restatement
-(``tests/_multvae_restatement.py``) judged by float64, byte-identical reruns and restores, the order and the noise,
-the annealing schedule, scoring, quality on the planted data, early stopping, and the fitted model through the fused
-evaluator and the serving layer."""
+(``tests/_multvae_restatement.py``) judged by float64 (the inputs: ``tests/_multvae_cases.py``), a batch larger than
+the handle was sized for and a smaller one after it, the divergence flag, byte-identical reruns and restores, the
+order and the noise, the annealing schedule, scoring (in ragged chunks, at large logits), quality on the planted data,
+early stopping, and the fitted model through the fused evaluator and the serving layer."""
 import io
 
 import numpy as np
 import pytest
 import scipy.sparse as sps
 
+import _multvae_cases as K
 import _multvae_restatement as R
 from _bpr_restatement import ndcg_at, planted_split
+from _multvae_cases import LR, batch_matrix, explicit_noise, random_start
 from conftest import assert_float64_bar
 from irspack_amd.recommenders import MultVAERecommender, TopPopRecommender
 from irspack_amd.recommenders.multvae import STATE_TABLES, TABLES, MultVAETrainer
 
 pytestmark = pytest.mark.gpu
-
-LR = 1e-2
 
 
 def same_bytes(a, b):
@@ -24,70 +25,11 @@ def same_bytes(a, b):
         all(a[n].tobytes() == b[n].tobytes() for n in STATE_TABLES)
 
 
-# ---- the data of the single-update tests ---------------------------------------------------------------------------
-def batch_matrix(n, n_items, seed):
-    """n rows: non-binary values at density 0.15; row 0 empty; row 1 with every item but item 3, which no row has
-    (the row is long enough for every wave of the encoder kernel); an explicit zero stored in row 2"""
-    rng = np.random.default_rng(seed)
-    D = (rng.random((n, n_items)) < 0.15) * rng.choice([0.5, 1.0, 2.0, 3.0], (n, n_items))
-    if n >= 3:
-        D[0] = 0
-    D[min(1, n - 1)] = rng.choice([0.5, 1.0, 2.0], n_items)
-    D[:, 3] = 0
-    X = sps.csr_matrix(D.astype(np.float32))
-    if n >= 3 and X.indptr[3] > X.indptr[2]:
-        X.data[X.indptr[2]] = 0.0  # (stays stored)
-    return X
-
-
-def random_start(n_items, H, L, Hd, seed, moments=True):
-    """float32 tables at their initial scale, biases and moments that are not zero, three updates done"""
-    rng = np.random.RandomState(seed)
-    state = R.initial_state(n_items, H, L, Hd, rng, np.float32)
-    for n in TABLES:
-        if n.startswith("b"):
-            state[n] = (0.1 * rng.standard_normal(state[n].shape)).astype(np.float32)
-        if moments:
-            state["m" + n] = (1e-3 * rng.standard_normal(state[n].shape)).astype(np.float32)
-            state["v" + n] = (1e-5 * rng.random_sample(state[n].shape)).astype(np.float32)
-    state["n_updates"] = 3 if moments else 0
-    return state
-
-
-MIN_ACTIVATION = 3e-3
-
-
-def conditioned_start(X, users, keep, eps, p, n_items, H, L, Hd, seed):
-    """``random_start`` at the first seed (``seed``, ``seed + 1000``, ...) whose float64 forward pass has no column
-    of h1, z or h2 of norm below ``MIN_ACTIVATION`` over the batch.  Such a column multiplies a whole row of a weight
-    gradient (with one batch row: dW4[j] = h2[j] g), and a float32 activation is known to 2^-24 of its inputs'
-    magnitude (about 1) however it was summed - so the row is relatively off by about 1e-7 / |activation| in ANY
-    float32 implementation, the restatement's included, and which of two is nearer to float64 there is chance.
-    3e-3 keeps that a third of the bar's 1e-4.  The rule looks at the float64 restatement alone."""
-    x, dense = np.asarray(X[users].todense()), R.dense_keep(X, users, keep)
-    for attempt in range(200):
-        start = random_start(n_items, H, L, Hd, seed + 1000 * attempt)
-        f = R.forward(start, x, dense, eps, p)
-        if min(float(np.linalg.norm(f[k], axis=0).min()) for k in ("h1", "z", "h2")) >= MIN_ACTIVATION:
-            return start
-    raise AssertionError("no well-conditioned start found")
-
-
 def make_trainer(X, H, Hd, L, p, **kw):
     args = dict(l2_regularizer=0.0, kl_anneal_goal=0.2, anneal_end_epoch=2, minibatch_size=max(X.shape[0], 1),
                 learning_rate=LR)
     args.update(kw)
     return MultVAETrainer(X, L, H, Hd, p, **args)
-
-
-def explicit_noise(X, users, L, p, seed, drop_row=None):
-    rng = np.random.default_rng(seed)
-    deg = np.diff(X.indptr)[users]
-    keep = (rng.random(int(deg.sum())) >= p).astype(np.uint8) if p > 0 else np.ones(int(deg.sum()), np.uint8)
-    if drop_row is not None and p > 0:
-        at = int(deg[:drop_row].sum())
-        keep[at:at + deg[drop_row]] = 0
-    return keep, rng.standard_normal((len(users), L)).astype(np.float32)
 
 
 def compare_update(trainer, X, start, users, keep, eps, p, klc, what):
@@ -122,36 +64,59 @@ def slabs():
 
 
 def update_cases():
-    """a covering selection of (I, H, Hd, L, n, dropout_p, klc): every value of every axis the issue names, the item
-    counts with the ragged fourth dh2 slab and the batch with two dW4 slabs and a remainder read from stats"""
-    dh2, dw4 = slabs()
-    i_big, n_big = 3 * dh2 + 37, 2 * dw4 + 9
-    return [
-        (70, 1, 1, 1, 1, 0.0, 0.0), (70, 5, 33, 3, 7, 0.5, 0.2), (70, 33, 5, 16, 100, 0.5, 0.0),
-        (70, 64, 130, 65, 7, 0.0, 0.2), (70, 130, 64, 1, 100, 0.5, 0.2), (70, 130, 1, 65, 100, 0.0, 0.2),
-        (70, 64, 64, 3, 1, 0.5, 0.2), (257, 1, 5, 3, 100, 0.5, 0.2), (257, 5, 1, 16, 1, 0.5, 0.0),
-        (257, 33, 64, 65, 7, 0.5, 0.2), (257, 64, 33, 1, 100, 0.0, 0.0), (257, 130, 130, 16, 100, 0.5, 0.2),
-        (257, 1, 130, 3, 7, 0.0, 0.2), (257, 64, 64, 16, n_big, 0.5, 0.2), (257, 5, 130, 1, n_big, 0.0, 0.0),
-        (i_big, 33, 130, 3, 7, 0.5, 0.2), (i_big, 64, 64, 16, 100, 0.0, 0.2), (i_big, 5, 5, 1, n_big, 0.5, 0.0),
-        (i_big, 130, 33, 65, 1, 0.5, 0.2), (i_big, 1, 64, 16, 100, 0.5, 0.2),
-    ]
+    """``_multvae_cases.update_cases`` at the slab sizes that stats report"""
+    return K.update_cases(*slabs())
 
 
 @pytest.mark.parametrize("case", range(20))
 def test_one_update_against_the_restatement(case):
     I, H, Hd, L, n, p, klc = update_cases()[case]
     dh2, dw4 = slabs()
-    X = batch_matrix(n, I, 100 + case)
+    X, users, keep, eps, start = K.case_inputs(update_cases()[case], case, wide=False)
     trainer = make_trainer(X, H, Hd, L, p)
     st = trainer.stats()
     assert (st["dh2_slab"], st["dw4_slab"]) == (dh2, dw4)
-    users = np.random.default_rng(case).permutation(n).astype(np.int32)
-    drop = int(np.argmax(np.diff(X.indptr)[users] > 0)) if n >= 3 else None
-    keep, eps = explicit_noise(X, users, L, p, case, drop_row=drop)
-    start = conditioned_start(X, users, keep, eps, p, I, H, L, Hd, 200 + case)
     got, _ = compare_update(trainer, X, start, users, keep, eps, p, klc, f"case {case} {update_cases()[case]}")
     assert got["W1"][3].tobytes() != start["W1"][3].tobytes()  # (Adam moves a row with a zero gradient by its momentum)
     trainer.close()
+
+
+@pytest.mark.parametrize("case", range(12))
+def test_wide_update_against_the_restatement(case):
+    """``_multvae_cases.wide_cases``: two and three passes of the sparse kernels, two of the latent kernel, five tiles
+    of 2 L and of Hd + 1, n and I at a slab, a tile and a BK step and one past, 64 dh2 slabs and the doubled slab"""
+    dh2, dw4 = slabs()
+    shape = K.wide_cases(dh2, dw4)[case]
+    I, H, Hd, L, n, p, klc = shape
+    X, users, keep, eps, start = K.case_inputs(shape, case, wide=True)
+    trainer = make_trainer(X, H, Hd, L, p)
+    st = trainer.stats()
+    assert (st["dh2_slab"], st["dw4_slab"]) == (K.dh2_slab(I), dw4) and dh2 == K.dh2_slab(70)
+    assert (-(-I // st["dh2_slab"]), -(-n // st["dw4_slab"])) == K.WIDE_SLABS[case][::2]
+    got, _ = compare_update(trainer, X, start, users, keep, eps, p, klc, f"wide case {case} {shape}")
+    assert got["W1"][3].tobytes() != start["W1"][3].tobytes()  # (Adam moves a row with a zero gradient by its momentum)
+    trainer.close()
+
+
+def test_a_small_batch_after_a_larger_one():
+    """a handle sized for 8 rows takes 300 (the work buffers regrow; two dW4 slabs and 44 rows), then 5, the empty and
+    the full row among them, with rows 5 .. 299 of every work buffer left over from before: both against the
+    restatement, and both byte for byte what a handle sized for 300 rows from the start gives - the bytes of a step
+    depend on the tiling, and the tiling on n, I and the widths, not on the capacity"""
+    c = K.REGROW
+    X, batches = K.regrowth_inputs()
+    grown = make_trainer(X, c["H"], c["Hd"], c["L"], c["p"], minibatch_size=c["first_capacity"])
+    sized = make_trainer(X, c["H"], c["Hd"], c["L"], c["p"], minibatch_size=c["rows"])
+    for users, keep, eps, start in batches:
+        got, _ = compare_update(grown, X, start, users, keep, eps, c["p"], c["klc"], f"regrown, {users.size} rows")
+        grads = grown.gradients()
+        sized.set_state(start)
+        sized.step_batch(users, keep, eps, c["klc"])
+        assert same_bytes(got, sized.get_state())
+        other = sized.gradients()
+        assert all(grads[n].tobytes() == other[n].tobytes() for n in TABLES)
+    grown.close()
+    sized.close()
 
 
 def test_softmax_at_large_logits():
@@ -198,6 +163,37 @@ def test_five_consecutive_updates():
         rows = (1, -1) if n[-2] == "b" else (got[n].shape[0], -1)
         assert_float64_bar(got[n].reshape(rows), ref32[n].reshape(rows), ref64[n].reshape(rows), f"five updates {n}",
                            test="multvae_five_updates")
+    trainer.close()
+
+
+def test_divergence_is_reported_and_set_state_recovers():
+    """One batch row, p = 0, klc = 0: the gradients are linear in the row's stored values, and the largest
+    contribution to the fixed-point sums of W1 is max |db1| (``_multvae_cases.divergence_inputs``).  User 0 is the
+    row scaled to bring that into (64, 128]: a legal step, summed correctly at scale 2^44.  User 1 is the row scaled
+    to [512, 1024): past the cap of 2^8, a reported error with every value finite.  ``set_state`` clears the flag and
+    the sums: the next legal step gives the bytes of a fresh handle."""
+    c, d = K.DIVERGENCE, K.divergence_inputs()
+    X, start, keep, eps = d["X"], d["start"], d["keep"], d["eps"]
+    legal, diverging = np.array([0], dtype=np.int32), np.array([1], dtype=np.int32)
+    fresh = make_trainer(X, c["H"], c["Hd"], c["L"], c["p"])
+    assert fresh.stats()["scale_log2"] == 44
+    want, _ = compare_update(fresh, X, start, legal, keep, eps, c["p"], c["klc"], "a contribution of 2^6 .. 2^7")
+    want_g = fresh.gradients()
+    top = float(np.abs(want_g["b1"]).max())
+    print("max |db1| of the legal step on the device:", top)
+    assert 64.0 < top <= 128.0
+    trainer = make_trainer(X, c["H"], c["Hd"], c["L"], c["p"])
+    trainer.set_state(start)
+    with pytest.raises(RuntimeError, match="diverged"):
+        trainer.step_batch(diverging, None, eps, c["klc"])
+    with pytest.raises(RuntimeError, match="diverged"):  # (the flag stays up: the state is no longer usable)
+        trainer.step_batch(legal, None, eps, c["klc"])
+    trainer.set_state(start)
+    trainer.step_batch(legal, None, eps, c["klc"])
+    assert same_bytes(want, trainer.get_state())
+    got_g = trainer.gradients()
+    assert all(got_g[n].tobytes() == want_g[n].tobytes() for n in TABLES)
+    fresh.close()
     trainer.close()
 
 
@@ -370,6 +366,72 @@ def test_scoring():
     assert np.abs(total - 1).max() <= 400 * 2.0 ** -24 * 4  # float32 rounding of I terms
     removed = model.get_score_remove_seen(np.array([3]))
     assert np.isneginf(removed[0, X_train[3].indices]).all()
+
+
+def test_scores_and_factors_in_ragged_chunks():
+    """21 cold rows through a handle of 8 rows (chunks of 8, 8 and 5; empty rows first, at the head of a chunk and
+    last; the full row before a chunk's head, so that the next chunk's entries begin far into the arrays): scores,
+    h2 and lse against the restatement, the factor product against the scores, and every row the same bytes
+    whichever chunk and position it is computed at"""
+    c = K.SCORING
+    I, H, Hd, L, cap = c["I"], c["H"], c["Hd"], c["L"], c["capacity"]
+    X = batch_matrix(c["users"], I, 42)
+    state = random_start(I, H, L, Hd, 43)
+    cold = K.ragged_cold_rows()
+    dense = np.asarray(cold.todense())
+    chunked, whole = make_trainer(X, H, Hd, L, 0.5, minibatch_size=cap), make_trainer(X, H, Hd, L, 0.5)
+    for t in (chunked, whole):
+        t.set_state(state)
+    got = chunked.score(cold)
+    assert got.dtype == np.float32 and got.shape == (21, I) and np.isfinite(got).all()
+    assert_float64_bar(got, R.eval_scores(state, dense, np.float32), R.eval_scores(state, dense, np.float64),
+                       "ragged chunks: log-softmax", test="multvae_scoring")
+    h2, lse = chunked.encode(cold)
+    assert h2.shape == (21, Hd) and lse.shape == (21,) and h2.dtype == lse.dtype == np.float32
+    (h32, l32), (h64, l64) = (R.eval_hidden(state, dense, d) for d in (np.float32, np.float64))
+    assert_float64_bar(h2, h32, h64, "ragged chunks: h2", test="multvae_scoring")
+    assert_float64_bar(lse[:, None], K.log_sum_exp(l32)[:, None], K.log_sum_exp(l64)[:, None], "ragged chunks: lse",
+                       test="multvae_scoring")
+    # the two factor tables multiply to the scores
+    k = Hd + 2
+    Z = np.concatenate([h2, np.ones((21, 1), np.float32), -lse[:, None]], axis=1).astype(np.float64)
+    Ct = np.concatenate([state["W4"], state["b4"][None, :], np.ones((1, I), np.float32)], axis=0).astype(np.float64)
+    bound = 4.0 * k * 2.0 ** -24 * (np.abs(Z) @ np.abs(Ct)).max(axis=1)
+    assert (np.abs(Z @ Ct - got).max(axis=1) <= bound).all()
+    # one chunk of 21 rows, and three rows alone: the same bytes
+    w_h2, w_lse = whole.encode(cold)
+    assert whole.score(cold).tobytes() == got.tobytes() and w_h2.tobytes() == h2.tobytes() and w_lse.tobytes() == lse.tobytes()
+    alone = [c["full"], 8, 20]
+    for t in (chunked, whole):
+        a_h2, a_lse = t.encode(cold[alone])
+        assert t.score(cold[alone]).tobytes() == got[alone].tobytes()
+        assert a_h2.tobytes() == h2[alone].tobytes() and a_lse.tobytes() == lse[alone].tobytes()
+    none = chunked.score(sps.csr_matrix((0, I), dtype=np.float32))
+    assert none.shape == (0, I) and none.dtype == np.float32
+    chunked.close()
+    whole.close()
+
+
+def test_log_softmax_scores_at_large_logits():
+    """the state of ``test_softmax_at_large_logits`` with [W4; b4] scaled until the evaluation logits of the scored
+    rows span beyond +-60: SM_LOG_SOFTMAX is finite everywhere and inside the bar"""
+    I, H, Hd, L, n = 257, 33, 33, 3, 40
+    X = batch_matrix(n, I, 7)
+    state = random_start(I, H, L, Hd, 8)
+    dense = np.asarray(X.todense())
+    span = float(np.abs(R.eval_hidden(state, dense)[1]).max())
+    state["W4"] = (state["W4"] * (80.0 / span)).astype(np.float32)
+    state["b4"] = (state["b4"] * (80.0 / span)).astype(np.float32)
+    lg = R.eval_hidden(state, dense)[1]
+    print("logits span", float(lg.min()), float(lg.max()))
+    assert lg.max() > 60 and lg.min() < -60
+    trainer = make_trainer(X, H, Hd, L, 0.5, minibatch_size=16)  # (chunks of 16, 16 and 8)
+    trainer.set_state(state)
+    got = trainer.score(X)
+    assert got.shape == (n, I) and np.isfinite(got).all()
+    assert_float64_bar(got, R.eval_scores(state, dense, np.float32), R.eval_scores(state, dense, np.float64),
+                       "large logits: log-softmax", test="multvae_scoring")
+    trainer.close()
 
 
 def test_quality_on_the_planted_split():
