@@ -459,6 +459,41 @@ irs_status irs_eval_get_metrics_factors(irs_evaluator *e, int64_t begin, int64_t
                                         const int32_t *mask_indices, int32_t n_cutoffs,
                                         const int64_t *cutoffs, int64_t offset,
                                         int32_t recall_with_cutoff, irs_metrics *out, int64_t *item_cnt);
+/* The three model calls for a model that scores fewer columns than the evaluator ranks (EvaluatorWithColdUser with
+ * feature-only items behind the training items, evaluator.py:623-634): the item operand covers the leading
+ * n_scored columns, 1 <= n_scored <= n_items - w_* / w is W [n_profile_cols, n_scored], item_factors is
+ * [n_scored, k] - the scores go to those columns of a block whose rows stay n_items wide, and the columns
+ * n_scored .. n_items hold -inf before the block is masked and ranked, so they are never recommended.  With
+ * n_scored == n_items these are the calls above.  `running` of the factor call (NULL, or one irs_metrics per
+ * cutoff): the sums of the users that earlier calls covered; the call merges its 128-user chunks onto them and
+ * returns the continued sums in out[c], so users handed over in several calls of whole chunks (a fold-in per
+ * call) are summed as one call sums them.  item_cnt is this call's alone. */
+irs_status irs_eval_get_metrics_similarity_scored(irs_evaluator *e, int64_t begin, int64_t end,
+                                                  int64_t n_model_users, int64_t n_profile_cols,
+                                                  const int64_t *x_indptr, const int32_t *x_indices,
+                                                  const double *x_data, const int64_t *w_indptr,
+                                                  const int32_t *w_indices, const double *w_data,
+                                                  int64_t n_scored, const int64_t *mask_indptr,
+                                                  const int32_t *mask_indices, int32_t n_cutoffs,
+                                                  const int64_t *cutoffs, int64_t offset,
+                                                  int32_t recall_with_cutoff, irs_metrics *out,
+                                                  int64_t *item_cnt);
+irs_status irs_eval_get_metrics_dense_similarity_scored(irs_evaluator *e, int64_t begin, int64_t end,
+                                                        int64_t n_model_users, int64_t n_profile_cols,
+                                                        const int64_t *x_indptr, const int32_t *x_indices,
+                                                        const double *x_data, int32_t w_is_f64, const void *w,
+                                                        int64_t n_scored, const int64_t *mask_indptr,
+                                                        const int32_t *mask_indices, int32_t n_cutoffs,
+                                                        const int64_t *cutoffs, int64_t offset,
+                                                        int32_t recall_with_cutoff, irs_metrics *out,
+                                                        int64_t *item_cnt);
+irs_status irs_eval_get_metrics_factors_scored(irs_evaluator *e, int64_t begin, int64_t end,
+                                               int64_t n_model_users, int32_t k, const float *user_factors,
+                                               const float *item_factors, int64_t n_scored,
+                                               const irs_metrics *running, const int64_t *mask_indptr,
+                                               const int32_t *mask_indices, int32_t n_cutoffs,
+                                               const int64_t *cutoffs, int64_t offset,
+                                               int32_t recall_with_cutoff, irs_metrics *out, int64_t *item_cnt);
 /* Stream time of the last irs_eval_get_metrics_dense_similarity / _factors call by phase, in milliseconds
  * (measurement only): ms[0] uploads, ms[1] scoring, ms[2] masking, ms[3] ranking and folding. */
 irs_status irs_eval_last_phases(irs_evaluator *e, double *ms);
@@ -607,6 +642,14 @@ irs_status irs_truncsvd_project(irs_truncsvd *t, float *gram_out);
 irs_status irs_truncsvd_finish(irs_truncsvd *t, const float *rot, int64_t k, float *z_out, float *components_out);
 irs_status irs_truncsvd_stats(irs_truncsvd *t, irs_truncsvd_stats_t *out);
 irs_status irs_truncsvd_destroy(irs_truncsvd *t);
+/* The fold-in of rows the fit has not seen (TruncatedSVD.transform: z = X @ components_^T), stateless: X is CSR
+ * [rows, n_items] (float32, sorted, no duplicates, finite), item_factors the table components_^T [n_items, k]
+ * row-major, 1 <= k <= 576, out [rows, k].  One sparse x block product with the row sums in double; every element
+ * is rounded to float32 once, also in a row long enough to be split.  The sums have a fixed order: the result is
+ * a function of the arguments, identical from call to call. */
+irs_status irs_truncsvd_transform(int64_t rows, int64_t n_items, const int64_t *indptr, const int32_t *indices,
+                                  const float *data, int64_t k, const float *item_factors, int32_t device,
+                                  float *out);
 
 /* ------------------------------------------------------------------ NMF
  * NMFRecommender (src/irspack/recommenders/nmf.py: sklearn.decomposition.NMF, solver "cd", Frobenius loss,

@@ -233,6 +233,7 @@ EXPORTED_SYMBOLS = [
     "irs_truncsvd_finish",
     "irs_truncsvd_stats",
     "irs_truncsvd_destroy",
+    "irs_truncsvd_transform",
     "irs_nmf_fit",
     "irs_bpr_create",
     "irs_bpr_run_epochs",
@@ -261,6 +262,9 @@ EXPORTED_SYMBOLS = [
     "irs_eval_get_metrics_similarity",
     "irs_eval_get_metrics_dense_similarity",
     "irs_eval_get_metrics_factors",
+    "irs_eval_get_metrics_similarity_scored",
+    "irs_eval_get_metrics_dense_similarity_scored",
+    "irs_eval_get_metrics_factors_scored",
     "irs_eval_last_phases",
     "irs_eval_get_metrics_ials",
     "irs_eval_cache_mask",
@@ -299,6 +303,8 @@ ARGTYPES = {
     "irs_truncsvd_finish": [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float)],
     "irs_truncsvd_stats": [C.c_void_p, C.c_void_p],
     "irs_truncsvd_destroy": [C.c_void_p],
+    "irs_truncsvd_transform": [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                               C.c_int64, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float)],
     "irs_nmf_fit": [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int64,
                     C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_float, C.c_double,
                     C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_void_p],
@@ -338,6 +344,19 @@ ARGTYPES = {
     "irs_eval_get_metrics_factors": [
         C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float),
         C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int64), C.c_int64, C.c_int32,
+        C.c_void_p, C.POINTER(C.c_int64)],
+    "irs_eval_get_metrics_similarity_scored": [
+        C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+        C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int64,
+        C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int64), C.c_int64, C.c_int32,
+        C.c_void_p, C.POINTER(C.c_int64)],
+    "irs_eval_get_metrics_dense_similarity_scored": [
+        C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+        C.POINTER(C.c_double), C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32,
+        C.POINTER(C.c_int64), C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)],
+    "irs_eval_get_metrics_factors_scored": [
+        C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64,
+        C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int64), C.c_int64, C.c_int32,
         C.c_void_p, C.POINTER(C.c_int64)],
     "irs_eval_last_phases": [C.c_void_p, C.POINTER(C.c_double)],
     "irs_serve_create_similarity": [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),

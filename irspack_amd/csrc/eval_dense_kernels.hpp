@@ -31,7 +31,8 @@ __global__ __launch_bounds__(64) void dense_sim_score_kernel(const int64_t *__re
                                                              const double *__restrict__ x_val,
                                                              const TW *__restrict__ w, int64_t row0, int64_t m_rows,
                                                              int64_t n_items, double *__restrict__ out,
-                                                             const int32_t *__restrict__ order) {
+                                                             const int32_t *__restrict__ order,
+                                                             int64_t ld) {  // ld >= n_items: row stride of `out`
   const int lane = threadIdx.x;
   const int64_t unit = blockIdx.x;
   const int64_t strip = unit / m_rows;
@@ -76,7 +77,7 @@ __global__ __launch_bounds__(64) void dense_sim_score_kernel(const int64_t *__re
       }
     }
   }
-  double *dst = out + r * n_items + c0;
+  double *dst = out + r * ld + c0;
 #pragma unroll
   for (int c = 0; c < DS_COLS; c++)
     if (lane + 64 * c < width) dst[lane + 64 * c] = acc[c];

@@ -189,6 +189,16 @@ inline int64_t rows_per_f32_block(int64_t ni, const char *cap_env, bool round_en
   return std::min<int64_t>(block_cap, std::max<int64_t>(floor_rows, fit >= 1024 ? fit / 1024 * 1024 : fit));
 }
 
+// The width of a model call that scores fewer columns than the evaluator ranks (the *_scored entries): the model's
+// item operand covers the leading n_scored of the evaluator's n_items columns - W is [profile columns, n_scored],
+// an item table [n_scored, k] - and the score kernels write those columns of a block whose row stride stays
+// n_items; the columns [n_scored, n_items) hold -inf before the block is masked and ranked (a cold-user evaluator's
+// feature-only items, evaluator.py:623-634), and the ranking kernels end a list at the first -inf.
+inline int64_t scored_width(int64_t n_scored, int64_t n_items) {
+  check_arg(n_scored > 0 && n_scored <= n_items, "n_scored must lie in 1 .. n_items.");
+  return n_scored;
+}
+
 // The rows of a CSR W [n_rows, n_cols] (pointers already checked): a column outside [0, n_cols), a row whose columns
 // do not strictly increase and - `want_duplicates`: such rows are sorted to find out - a column stored twice in a row.
 struct WeightRowsScan { bool out_of_range, unsorted, duplicate; };

@@ -215,5 +215,16 @@ __global__ void mask_block_kernel(T *scores, int64_t rows, int64_t n_items,
   }
 }
 
+// scores[row, n_scored .. n_items) = -inf: the trailing columns of a block that the model does not score (the
+// feature-only items of a cold-user evaluation, evaluator.py:623-634); the score kernels wrote the columns below
+// n_scored of the same rows.  One workgroup per row.
+template <class T>
+__global__ void fill_unscored_kernel(T *scores, int64_t rows, int64_t n_items, int64_t n_scored) {
+  const int64_t row = blockIdx.x;
+  if (row >= rows) return;
+  for (int64_t j = n_scored + threadIdx.x; j < n_items; j += blockDim.x)
+    scores[row * n_items + j] = -std::numeric_limits<T>::infinity();
+}
+
 }  // namespace eval
 }  // namespace irs

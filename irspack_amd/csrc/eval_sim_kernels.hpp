@@ -56,7 +56,8 @@ __global__ __launch_bounds__(64) void sim_score_kernel(const int64_t *__restrict
                                                        const double *__restrict__ w_val, int64_t w_last, int64_t row0,
                                                        int64_t n_items, int32_t n_tiles, double *__restrict__ out,
                                                        const int32_t *__restrict__ w_tptr,
-                                                       const int32_t *__restrict__ order) {
+                                                       const int32_t *__restrict__ order,
+                                                       int64_t ld) {  // ld >= n_items: row stride of `out`
   __shared__ double acc[SIM_TILE];
   const int lane = threadIdx.x;
   const int64_t unit = blockIdx.x;
@@ -129,7 +130,7 @@ __global__ __launch_bounds__(64) void sim_score_kernel(const int64_t *__restrict
       }
     }
   }
-  double *dst = out + r * n_items + c0;
+  double *dst = out + r * ld + c0;
   for (int k = lane; k < width; k += 64) dst[k] = acc[k];
 }
 

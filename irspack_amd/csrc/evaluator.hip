@@ -44,7 +44,7 @@ using namespace irs::eval;
 // exported by ials.hip: user[0:m] @ item^T of factor tables the CALLER holds on the device ([rows, KP]
 // row-major, KP a multiple of 32, padded columns zero) through the fp32 MFMA tiles of the iALS scores
 extern "C" irs_status irs_gk_scores_device_(const float *user, const float *item, int32_t KP, int64_t m,
-                                            int64_t n_items, float *device_out, void *stream);
+                                            int64_t n_items, float *device_out, int64_t ld, void *stream);
 // exported by ials.hip for the fused path
 extern "C" irs_status irs_ials_scores_device_(irs_ials_trainer *t, int64_t begin, int64_t end,
                                               float *device_out, void **stream_out,
@@ -330,13 +330,20 @@ struct CutoffTotals {
   enum Order { CHUNKS, BLOCKS } order;
   DeviceBuffer<irs_metrics> m;
   DeviceBuffer<unsigned long long> cnt;
-  CutoffTotals(Order order_, int32_t n_cutoffs, int64_t ni, int64_t *item_cnt, hipStream_t s) : order(order_) {
+  // `running` (CHUNKS only; one irs_metrics per cutoff, or null): the sums of the users before this call's - the
+  // call's chunks are merged onto them, so a caller that hands its users over in several calls of whole chunks gets
+  // the sums of one call (the item counts are integers and start from zero either way: the caller adds them)
+  CutoffTotals(Order order_, int32_t n_cutoffs, int64_t ni, int64_t *item_cnt, hipStream_t s,
+               const irs_metrics *running = nullptr)
+      : order(order_) {
     std::fill(item_cnt, item_cnt + static_cast<int64_t>(std::max(n_cutoffs, 0)) * ni, int64_t(0));
     const size_t nc = static_cast<size_t>(std::max(n_cutoffs, 1));
     m.alloc(nc);
     cnt.alloc(nc * static_cast<size_t>(std::max<int64_t>(ni, 1)));
     m.zero(s);
     cnt.zero(s);
+    if (running != nullptr && n_cutoffs > 0)
+      IRS_HIP(hipMemcpyAsync(m.ptr, running, sizeof(irs_metrics) * static_cast<size_t>(n_cutoffs), hipMemcpyHostToDevice, s));
   }
   template <class T>
   void add_block(irs_evaluator *e, const T *scores, int64_t rows, int32_t n_cutoffs, const int64_t *cutoffs,
@@ -992,38 +999,60 @@ void build_tile_table(DeviceBuffer<int32_t> &tptr, const DeviceBuffer<int64_t> &
 }
 
 // scores of the rows row0 .. row0 + m of `x` (launched in `order`, relative to row0) into out [m, ni]
+// (`ni`: the columns scored = W's width; `ld` >= ni: the row stride of `out`, 0 = ni)
 void launch_sim_scores(const ProfileView &x, const SparseWeightsView &w, int64_t row0, int64_t m, int64_t ni, double *out,
-                       const int32_t *order, hipStream_t s) {
+                       const int32_t *order, hipStream_t s, int64_t ld = 0) {
   hipLaunchKernelGGL(w.tptr ? sim_score_kernel<true> : sim_score_kernel<false>, dim3(static_cast<unsigned>(m * w.n_tiles)),
                      dim3(64), 0, s, x.ptr, x.idx, x.val, w.ptr, w.idx, w.val, std::max<int64_t>(w.nnz - 1, 0), row0, ni,
-                     w.n_tiles, out, w.tptr, order);
+                     w.n_tiles, out, w.tptr, order, ld > 0 ? ld : ni);
 }
 void launch_dense_scores(const ProfileView &x, const void *w, bool w_is_f64, int64_t row0, int64_t m, int64_t ni,
-                         double *out, const int32_t *order, hipStream_t s) {
+                         double *out, const int32_t *order, hipStream_t s, int64_t ld = 0) {
+  if (ld <= 0) ld = ni;
   const dim3 grid(static_cast<unsigned>(m * ceil_div(std::max<int64_t>(ni, 1), DS_STRIP)));
   if (w_is_f64)
     hipLaunchKernelGGL(dense_sim_score_kernel<double>, grid, dim3(64), 0, s, x.ptr, x.idx, x.val,
-                       static_cast<const double *>(w), row0, m, ni, out, order);
+                       static_cast<const double *>(w), row0, m, ni, out, order, ld);
   else
     hipLaunchKernelGGL(dense_sim_score_kernel<float>, grid, dim3(64), 0, s, x.ptr, x.idx, x.val,
-                       static_cast<const float *>(w), row0, m, ni, out, order);
+                       static_cast<const float *>(w), row0, m, ni, out, order, ld);
+}
+
+// the columns [ns, ni) of a block that a model call does not score (the *_scored entries with n_scored < n_items)
+template <class T> void fill_unscored(T *scores, int64_t m, int64_t ni, int64_t ns, hipStream_t s) {
+  if (ns >= ni || m <= 0) return;
+  hipLaunchKernelGGL(fill_unscored_kernel<T>, dim3(static_cast<unsigned>(m)), dim3(64), 0, s, scores, m, ni, ns);
+}
+
+// The width argument of the three model calls below: WHOLE_WIDTH = the evaluator's n_items (the entries without
+// `n_scored`, which also take an evaluator without items); anything else goes through scored_width().
+constexpr int64_t WHOLE_WIDTH = -1;
+inline int64_t width_of(int64_t n_scored, int64_t ni) { return n_scored == WHOLE_WIDTH ? ni : scored_width(n_scored, ni); }
+// what a *_scored entry checks before it hands over to the call it shares with the entry without `n_scored`
+irs_status check_scored_entry(const irs_evaluator *e, int64_t n_scored) {
+  return guard([&] {
+    check_arg(e != nullptr, "null argument.");
+    scored_width(n_scored, e->n_items);
+  });
 }
 
 }  // namespace
 extern "C" {
 
-irs_status irs_eval_get_metrics_similarity(irs_evaluator *e, int64_t begin, int64_t end, int64_t n_model_users,
-                                           int64_t n_profile_cols,
-                                           const int64_t *x_indptr, const int32_t *x_indices, const double *x_data,
-                                           const int64_t *w_indptr, const int32_t *w_indices, const double *w_data,
-                                           const int64_t *mask_indptr, const int32_t *mask_indices,
-                                           int32_t n_cutoffs, const int64_t *cutoffs, int64_t offset,
-                                           int32_t recall_with_cutoff, irs_metrics *out, int64_t *item_cnt) {
+static irs_status similarity_call(irs_evaluator *e, int64_t begin, int64_t end, int64_t n_model_users,
+                                  int64_t n_profile_cols, const int64_t *x_indptr,
+                                  const int32_t *x_indices, const double *x_data,
+                                  const int64_t *w_indptr, const int32_t *w_indices,
+                                  const double *w_data, int64_t n_scored, const int64_t *mask_indptr,
+                                  const int32_t *mask_indices, int32_t n_cutoffs,
+                                  const int64_t *cutoffs, int64_t offset, int32_t recall_with_cutoff,
+                                  irs_metrics *out, int64_t *item_cnt) {
   return guard([&] {
     check_arg(e && out && item_cnt && cutoffs && x_indptr && w_indptr, "null argument.");
     check_arg(0 <= begin && begin <= end && end <= n_model_users, "user range out of bounds.");
     check_arg(n_cutoffs >= 0, "negative count.");
     const int64_t rows = end - begin, ni = e->n_items;
+    const int64_t ns = width_of(n_scored, ni);  // W is [n_profile_cols, ns]; the block's row stride stays ni
     for (int32_t c = 0; c < n_cutoffs; c++) validate_call(e, rows, cutoffs[c], offset, 1);
     // the two CSR matrices: the profiles X [n_model_users, n_profile_cols] (rows begin .. end are read) and
     // W [n_profile_cols, n_items]: item-kNN / P3alpha / RP3beta: X = the training matrix, W item x item;
@@ -1040,7 +1069,7 @@ irs_status irs_eval_get_metrics_similarity(irs_evaluator *e, int64_t begin, int6
     // rows of W with strictly increasing columns (what every recommender of this package stores) are cut
     // into per-tile ranges on the device; any other W takes the whole-row walk.  (A column stored twice in a
     // row is not looked for here.)
-    const WeightRowsScan w_rows = scan_weight_rows(w_indptr, w_indices, np_, ni, false);
+    const WeightRowsScan w_rows = scan_weight_rows(w_indptr, w_indices, np_, ns, false);
     check_arg(!w_rows.out_of_range, "column index out of range.");
     const bool w_tiled = !w_rows.unsorted && w_nnz < (int64_t(1) << 31);
     IRS_HIP(hipSetDevice(e->device));
@@ -1061,7 +1090,7 @@ irs_status irs_eval_get_metrics_similarity(irs_evaluator *e, int64_t begin, int6
     // of the ML-20M shape, 29.6 GB of scores: 1 GB blocks 59.8 ms, 2 GB 50.1, 4 GB 44.5, 8 GB 42.6, one block
     // 40.5 - against 90 / 190 / 310 ms for the first call's allocation at 1 / 4 / 8 GB.)
     const int64_t per = rows_per_f64_block(ni, rows, false);
-    const int32_t n_tiles = sim_tiles(ni);
+    const int32_t n_tiles = sim_tiles(ns);
     CutoffTotals totals(CutoffTotals::BLOCKS, n_cutoffs, ni, item_cnt, s);
     if (rows > 0) e->score_buf.alloc(static_cast<size_t>(per) * ni * 8);
     DeviceBuffer<int32_t> d_wt;
@@ -1077,7 +1106,8 @@ irs_status irs_eval_get_metrics_similarity(irs_evaluator *e, int64_t begin, int6
     for (int64_t b = 0; b < rows; b += per) {
       const int64_t m = std::min(per, rows - b);
       double *scores = reinterpret_cast<double *>(e->score_buf.ptr);
-      launch_sim_scores(xv, wv, b, m, ni, scores, d_order.ptr + b, s);
+      launch_sim_scores(xv, wv, b, m, ns, scores, d_order.ptr + b, s, ni);
+      fill_unscored(scores, m, ni, ns, s);
       if (mask.ptr.ptr)
         hipLaunchKernelGGL(mask_block_kernel<double>, dim3(static_cast<unsigned>(m)), dim3(64), 0, s, scores, m, ni,
                            mask.ptr.ptr + b, mask.idx.ptr);
@@ -1088,18 +1118,49 @@ irs_status irs_eval_get_metrics_similarity(irs_evaluator *e, int64_t begin, int6
   });
 }
 
-irs_status irs_eval_get_metrics_dense_similarity(irs_evaluator *e, int64_t begin, int64_t end, int64_t n_model_users,
-                                                 int64_t n_profile_cols, const int64_t *x_indptr,
-                                                 const int32_t *x_indices, const double *x_data, int32_t w_is_f64,
-                                                 const void *w, const int64_t *mask_indptr,
-                                                 const int32_t *mask_indices, int32_t n_cutoffs, const int64_t *cutoffs,
-                                                 int64_t offset, int32_t recall_with_cutoff, irs_metrics *out,
-                                                 int64_t *item_cnt) {
+irs_status irs_eval_get_metrics_similarity(irs_evaluator *e, int64_t begin, int64_t end, int64_t n_model_users,
+                                           int64_t n_profile_cols,
+                                           const int64_t *x_indptr, const int32_t *x_indices, const double *x_data,
+                                           const int64_t *w_indptr, const int32_t *w_indices, const double *w_data,
+                                           const int64_t *mask_indptr, const int32_t *mask_indices,
+                                           int32_t n_cutoffs, const int64_t *cutoffs, int64_t offset,
+                                           int32_t recall_with_cutoff, irs_metrics *out, int64_t *item_cnt) {
+  return similarity_call(e, begin, end, n_model_users, n_profile_cols, x_indptr, x_indices,
+                         x_data, w_indptr, w_indices, w_data, WHOLE_WIDTH, mask_indptr,
+                         mask_indices, n_cutoffs, cutoffs, offset, recall_with_cutoff, out,
+                         item_cnt);
+}
+
+irs_status irs_eval_get_metrics_similarity_scored(irs_evaluator *e, int64_t begin, int64_t end, int64_t n_model_users,
+                                                  int64_t n_profile_cols, const int64_t *x_indptr,
+                                                  const int32_t *x_indices, const double *x_data,
+                                                  const int64_t *w_indptr, const int32_t *w_indices,
+                                                  const double *w_data, int64_t n_scored, const int64_t *mask_indptr,
+                                                  const int32_t *mask_indices, int32_t n_cutoffs,
+                                                  const int64_t *cutoffs, int64_t offset, int32_t recall_with_cutoff,
+                                                  irs_metrics *out, int64_t *item_cnt) {
+  const irs_status st = check_scored_entry(e, n_scored);
+  if (st != IRS_OK) return st;
+  return similarity_call(e, begin, end, n_model_users, n_profile_cols, x_indptr, x_indices, x_data, w_indptr, w_indices,
+                         w_data, n_scored, mask_indptr, mask_indices, n_cutoffs, cutoffs, offset, recall_with_cutoff,
+                         out, item_cnt);
+}
+
+static irs_status dense_similarity_call(irs_evaluator *e, int64_t begin, int64_t end,
+                                        int64_t n_model_users, int64_t n_profile_cols,
+                                        const int64_t *x_indptr, const int32_t *x_indices,
+                                        const double *x_data, int32_t w_is_f64, const void *w,
+                                        int64_t n_scored, const int64_t *mask_indptr,
+                                        const int32_t *mask_indices, int32_t n_cutoffs,
+                                        const int64_t *cutoffs, int64_t offset,
+                                        int32_t recall_with_cutoff, irs_metrics *out,
+                                        int64_t *item_cnt) {
   return guard([&] {
     check_arg(e && out && item_cnt && cutoffs && x_indptr, "null argument.");
     check_arg(0 <= begin && begin <= end && end <= n_model_users, "user range out of bounds.");
     check_arg(n_cutoffs >= 0, "negative count.");
     const int64_t rows = end - begin, ni = e->n_items, np_ = n_profile_cols;
+    const int64_t ns = width_of(n_scored, ni);  // W is [n_profile_cols, ns]; the block's row stride stays ni
     for (int32_t c = 0; c < n_cutoffs; c++) validate_call(e, rows, cutoffs[c], offset, 1);
     check_arg(np_ >= 0 && np_ < (int64_t(1) << 31), "bad profile width.");
     ProfileRows x;
@@ -1120,11 +1181,11 @@ irs_status irs_eval_get_metrics_dense_similarity(irs_evaluator *e, int64_t begin
     d_xi.upload(x_indices + x.first, static_cast<size_t>(x_nnz), s);
     d_xv.upload(x_data + x.first, static_cast<size_t>(x_nnz), s);
     if (rows > 0 && x_nnz > 0)
-      d_w.upload(static_cast<const char *>(w), static_cast<size_t>(np_) * ni * (w_is_f64 ? 8 : 4), s);
+      d_w.upload(static_cast<const char *>(w), static_cast<size_t>(np_) * ns * (w_is_f64 ? 8 : 4), s);
     CallMask mask;
     mask.upload(mask_indptr, mask_indices, rows, ni, true, s);
     const int64_t per = rows_per_f64_block(ni, rows, true);  // (whole chunks of the host loop)
-    const int64_t n_strips = ceil_div(std::max<int64_t>(ni, 1), DS_STRIP);
+    const int64_t n_strips = ceil_div(std::max<int64_t>(ns, 1), DS_STRIP);
     check_arg(per * n_strips < (int64_t(1) << 31), "score block too large for one launch.");
     CutoffTotals totals(CutoffTotals::CHUNKS, n_cutoffs, ni, item_cnt, s);
     DeviceBuffer<int32_t> d_order;
@@ -1142,7 +1203,8 @@ irs_status irs_eval_get_metrics_dense_similarity(irs_evaluator *e, int64_t begin
       if (x_nnz == 0)  // (no profile entry in the whole call: W was not uploaded, every score is 0)
         IRS_HIP(hipMemsetAsync(scores, 0, static_cast<size_t>(m) * ni * 8, s));
       else
-        launch_dense_scores(xv, d_w.ptr, w_is_f64 != 0, b, m, ni, scores, d_order.ptr + b, s);
+        launch_dense_scores(xv, d_w.ptr, w_is_f64 != 0, b, m, ns, scores, d_order.ptr + b, s, ni);
+      fill_unscored(scores, m, ni, ns, s);
       IRS_HIP(hipGetLastError());
       clock.mark(PH_SCORE);
       if (mask.ptr.ptr)
@@ -1158,17 +1220,47 @@ irs_status irs_eval_get_metrics_dense_similarity(irs_evaluator *e, int64_t begin
   });
 }
 
-irs_status irs_eval_get_metrics_factors(irs_evaluator *e, int64_t begin, int64_t end, int64_t n_model_users, int32_t k,
-                                        const float *user_factors, const float *item_factors,
-                                        const int64_t *mask_indptr, const int32_t *mask_indices, int32_t n_cutoffs,
-                                        const int64_t *cutoffs, int64_t offset, int32_t recall_with_cutoff,
-                                        irs_metrics *out, int64_t *item_cnt) {
+irs_status irs_eval_get_metrics_dense_similarity(irs_evaluator *e, int64_t begin, int64_t end, int64_t n_model_users,
+                                                 int64_t n_profile_cols, const int64_t *x_indptr,
+                                                 const int32_t *x_indices, const double *x_data, int32_t w_is_f64,
+                                                 const void *w, const int64_t *mask_indptr,
+                                                 const int32_t *mask_indices, int32_t n_cutoffs, const int64_t *cutoffs,
+                                                 int64_t offset, int32_t recall_with_cutoff, irs_metrics *out,
+                                                 int64_t *item_cnt) {
+  return dense_similarity_call(e, begin, end, n_model_users, n_profile_cols, x_indptr, x_indices,
+                               x_data, w_is_f64, w, WHOLE_WIDTH, mask_indptr, mask_indices,
+                               n_cutoffs, cutoffs, offset, recall_with_cutoff, out, item_cnt);
+}
+
+irs_status irs_eval_get_metrics_dense_similarity_scored(irs_evaluator *e, int64_t begin, int64_t end,
+                                                        int64_t n_model_users, int64_t n_profile_cols,
+                                                        const int64_t *x_indptr, const int32_t *x_indices,
+                                                        const double *x_data, int32_t w_is_f64, const void *w,
+                                                        int64_t n_scored, const int64_t *mask_indptr,
+                                                        const int32_t *mask_indices, int32_t n_cutoffs,
+                                                        const int64_t *cutoffs, int64_t offset,
+                                                        int32_t recall_with_cutoff, irs_metrics *out,
+                                                        int64_t *item_cnt) {
+  const irs_status st = check_scored_entry(e, n_scored);
+  if (st != IRS_OK) return st;
+  return dense_similarity_call(e, begin, end, n_model_users, n_profile_cols, x_indptr, x_indices, x_data, w_is_f64, w,
+                               n_scored, mask_indptr, mask_indices, n_cutoffs, cutoffs, offset, recall_with_cutoff,
+                               out, item_cnt);
+}
+
+static irs_status factors_call(irs_evaluator *e, int64_t begin, int64_t end, int64_t n_model_users,
+                               int32_t k, const float *user_factors, const float *item_factors,
+                               int64_t n_scored, const irs_metrics *running,
+                               const int64_t *mask_indptr, const int32_t *mask_indices,
+                               int32_t n_cutoffs, const int64_t *cutoffs, int64_t offset,
+                               int32_t recall_with_cutoff, irs_metrics *out, int64_t *item_cnt) {
   return guard([&] {
     check_arg(e && out && item_cnt && cutoffs, "null argument.");
     check_arg(0 <= begin && begin <= end && end <= n_model_users, "user range out of bounds.");
     check_arg(n_cutoffs >= 0, "negative count.");
     check_arg(k >= 1 && k <= 576, "the number of factors must lie in 1 .. 576.");
     const int64_t rows = end - begin, ni = e->n_items;
+    const int64_t ns = width_of(n_scored, ni);  // the item table is [ns, k]; the block's row stride stays ni
     for (int32_t c = 0; c < n_cutoffs; c++) validate_call(e, rows, cutoffs[c], offset, 1);
     check_arg((rows == 0 || user_factors) && (ni == 0 || item_factors), "null argument.");
     IRS_HIP(hipSetDevice(e->device));
@@ -1178,19 +1270,20 @@ irs_status irs_eval_get_metrics_factors(irs_evaluator *e, int64_t begin, int64_t
     const int32_t KP = (k + 31) / 32 * 32;
     DeviceBuffer<float> d_user, d_item;
     upload_padded(d_user, rows > 0 ? user_factors + begin * static_cast<int64_t>(k) : nullptr, rows, k, KP, s);
-    upload_padded(d_item, item_factors, ni, k, KP, s);
+    upload_padded(d_item, item_factors, ns, k, KP, s);
     CallMask mask;
     mask.upload(mask_indptr, mask_indices, rows, ni, true, s);
     // users scored and ranked per pass: as in irs_eval_get_metrics_ials, in whole chunks of the host loop
     const int64_t BLOCK = rows_per_f32_block(ni, "IRSPACK_AMD_EVAL_BLOCK", true, 1024);
-    CutoffTotals totals(CutoffTotals::CHUNKS, n_cutoffs, ni, item_cnt, s);
+    CutoffTotals totals(CutoffTotals::CHUNKS, n_cutoffs, ni, item_cnt, s, running);
     DeviceBuffer<float> &scores = e->fused_scores;
     if (rows > 0 && ni > 0) scores.alloc(static_cast<size_t>(std::min(BLOCK, rows)) * ni);
     clock.mark(PH_UPLOAD);
     for (int64_t b = 0; b < rows && ni > 0; b += BLOCK) {
       const int64_t m = std::min(BLOCK, rows - b);
-      if (irs_gk_scores_device_(d_user.ptr + b * KP, d_item.ptr, KP, m, ni, scores.ptr, s) != IRS_OK)
+      if (irs_gk_scores_device_(d_user.ptr + b * KP, d_item.ptr, KP, m, ns, scores.ptr, ni, s) != IRS_OK)
         throw std::runtime_error(irs_last_error());
+      fill_unscored(scores.ptr, m, ni, ns, s);
       clock.mark(PH_SCORE);
       if (mask.ptr.ptr)
         hipLaunchKernelGGL(mask_rows_kernel, dim3(static_cast<unsigned>(m)), dim3(64), 0, s, scores.ptr, m, ni,
@@ -1204,6 +1297,28 @@ irs_status irs_eval_get_metrics_factors(irs_evaluator *e, int64_t begin, int64_t
     totals.finish(e, n_cutoffs, out, item_cnt, s);
     clock.read(e->phase_ms);
   });
+}
+
+irs_status irs_eval_get_metrics_factors(irs_evaluator *e, int64_t begin, int64_t end, int64_t n_model_users, int32_t k,
+                                        const float *user_factors, const float *item_factors,
+                                        const int64_t *mask_indptr, const int32_t *mask_indices, int32_t n_cutoffs,
+                                        const int64_t *cutoffs, int64_t offset, int32_t recall_with_cutoff,
+                                        irs_metrics *out, int64_t *item_cnt) {
+  return factors_call(e, begin, end, n_model_users, k, user_factors, item_factors, WHOLE_WIDTH,
+                      nullptr, mask_indptr, mask_indices, n_cutoffs, cutoffs, offset,
+                      recall_with_cutoff, out, item_cnt);
+}
+
+irs_status irs_eval_get_metrics_factors_scored(irs_evaluator *e, int64_t begin, int64_t end, int64_t n_model_users,
+                                               int32_t k, const float *user_factors, const float *item_factors,
+                                               int64_t n_scored, const irs_metrics *running,
+                                               const int64_t *mask_indptr, const int32_t *mask_indices,
+                                               int32_t n_cutoffs, const int64_t *cutoffs, int64_t offset,
+                                               int32_t recall_with_cutoff, irs_metrics *out, int64_t *item_cnt) {
+  const irs_status st = check_scored_entry(e, n_scored);
+  if (st != IRS_OK) return st;
+  return factors_call(e, begin, end, n_model_users, k, user_factors, item_factors, n_scored, running, mask_indptr,
+                      mask_indices, n_cutoffs, cutoffs, offset, recall_with_cutoff, out, item_cnt);
 }
 
 irs_status irs_eval_last_phases(irs_evaluator *e, double *ms) {

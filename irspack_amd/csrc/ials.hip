@@ -1897,7 +1897,7 @@ irs_status irs_ials_scores_device_(irs_ials_trainer *t, int64_t begin, int64_t e
       hipLaunchKernelGGL(gk_user_scores_kernel, dim3(ceil_div(waves, 4)), dim3(256), 0, t->stream,
                          static_cast<const float *>(t->factor[0].ptr),
                          static_cast<const float *>(t->factor[1].ptr), t->KP, begin, m, t->n_items,
-                         device_out);
+                         device_out, t->n_items);
     } else {
       IRS_DISPATCH_ANY(t->T, {
         hipLaunchKernelGGL((user_scores_kernel<16 * TT>), dim3(ceil_div(waves, 4)), dim3(256), 0,
@@ -1912,17 +1912,18 @@ irs_status irs_ials_scores_device_(irs_ials_trainer *t, int64_t begin, int64_t e
 
 // Internal hook for evaluator.hip's factor-model path: user[0:m] @ item^T for factor tables that belong to
 // the caller (device, [rows, KP] row-major, KP a multiple of 32 with the padded columns zero), on the
-// caller's stream and current device.  Not part of the public ABI.
+// caller's stream and current device; `ld` >= n_items is the row stride of `device_out` (the columns from n_items
+// on are not written).  Not part of the public ABI.
 irs_status irs_gk_scores_device_(const float *user, const float *item, int32_t KP, int64_t m, int64_t n_items,
-                                 float *device_out, void *stream) {
+                                 float *device_out, int64_t ld, void *stream) {
   return guard([&] {
     check_arg(KP > 0 && KP % 32 == 0, "factor width must be a positive multiple of 32.");
-    check_arg(m >= 0 && n_items >= 0, "negative count.");
+    check_arg(m >= 0 && n_items >= 0 && ld >= n_items, "negative count.");
     if (m == 0 || n_items == 0) return;
     check_arg(user && item && device_out, "null argument.");
     const int64_t waves = ceil_div(m, 64) * ceil_div(n_items, 64);
     hipLaunchKernelGGL(gk_user_scores_kernel, dim3(ceil_div(waves, 4)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), user, item, KP, int64_t(0), m, n_items, device_out);
+                       static_cast<hipStream_t>(stream), user, item, KP, int64_t(0), m, n_items, device_out, ld);
     IRS_HIP(hipGetLastError());
   });
 }
@@ -1947,7 +1948,7 @@ irs_status irs_ials_scores_prefix_device_(irs_ials_trainer *t, int64_t begin, in
       hipLaunchKernelGGL(gk_user_scores_kernel, dim3(ceil_div(waves, 4)), dim3(256), 0, t->stream,
                          user_rows ? user_rows : static_cast<const float *>(t->factor[0].ptr),
                          item_rows ? item_rows : static_cast<const float *>(t->factor[1].ptr), t->KP,
-                         begin, m, n_prefix, device_out);
+                         begin, m, n_prefix, device_out, n_prefix);
     } else {
       IRS_DISPATCH_ANY(t->T, {
         hipLaunchKernelGGL((user_scores_kernel<16 * TT>), dim3(ceil_div(waves, 4)), dim3(256), 0,

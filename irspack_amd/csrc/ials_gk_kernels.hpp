@@ -620,7 +620,8 @@ __global__ void gk_gramian_finish_kernel(const float *__restrict__ P_raw, float 
 __global__ __launch_bounds__(256) void gk_user_scores_kernel(const float *__restrict__ user,
                                                              const float *__restrict__ item, int KP,
                                                              int64_t begin, int64_t m_rows,
-                                                             int64_t n_items, float *__restrict__ out) {
+                                                             int64_t n_items, float *__restrict__ out,
+                                                             int64_t ld) {  // ld >= n_items: row stride of `out`
   const int lane = threadIdx.x & 63;
   const int g = lane >> 4, m = lane & 15;
   const int64_t item_tiles = (n_items + 63) / 64;
@@ -673,7 +674,7 @@ __global__ __launch_bounds__(256) void gk_user_scores_kernel(const float *__rest
     for (int r = 0; r < 4; r++) {
       const int64_t row = ut * 64 + p * 16 + 4 * g + r;
       if (row >= m_rows) continue;
-      float *dst = out + row * n_items + col;
+      float *dst = out + row * ld + col;
 #pragma unroll
       for (int q = 0; q < 4; q++)
         if (col + q < n_items) dst[q] = acc[p][q][r];

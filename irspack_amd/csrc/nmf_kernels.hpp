@@ -108,7 +108,10 @@ static __global__ __launch_bounds__(SWEEP_ROWS) void nmf_sweep_kernel(float *W, 
 // rounded to float32 once, at the store: same segments, same lane layout, same order.  With a small `alpha` the
 // fit amplifies the rounding of XH and G by four orders of magnitude, and a float32 sum over a row
 // of 100 entries is ten roundings where the stored value allows one.
-template <int LPR, int NCH>
+// TP: the type of a split row's partial sums.  float (the fit): every segment is rounded, then the segments are added
+// in float (tsvd_spmm_reduce_kernel).  double (the truncated SVD's fold-in, irs_truncsvd_transform): the segments'
+// sums stay in double and nmf_spmm_reduce_f64_kernel rounds their sum - every row, split or not, is rounded once.
+template <int LPR, int NCH, class TP = float>
 static __global__ __launch_bounds__(256) void nmf_spmm_kernel(const int32_t *__restrict__ seg_row,
                                                               const int32_t *__restrict__ seg_begin,
                                                               const int32_t *__restrict__ seg_end,
@@ -116,7 +119,7 @@ static __global__ __launch_bounds__(256) void nmf_spmm_kernel(const int32_t *__r
                                                               const int32_t *__restrict__ idx,
                                                               const float *__restrict__ val,
                                                               const float *__restrict__ Q, int l_pad,
-                                                              float *__restrict__ Y, float *__restrict__ partial) {
+                                                              float *__restrict__ Y, TP *__restrict__ partial) {
   constexpr int G = 64 / LPR;
   const int s = static_cast<int>(blockIdx.x) * 4 + wave_index_in_block();
   if (s >= n_seg) return;
@@ -174,14 +177,45 @@ static __global__ __launch_bounds__(256) void nmf_spmm_kernel(const int32_t *__r
 #pragma unroll
       for (int x = 0; x < 4; x++) acc[0][x] += __shfl_down(acc[0][x], off);
   }
-  float4 *dst = reinterpret_cast<float4 *>(slot < 0 ? Y + static_cast<size_t>(row) * l_pad
-                                                    : partial + static_cast<size_t>(slot) * l_pad);
+  if constexpr (sizeof(TP) == 8) {
+    if (slot >= 0) {  // (wave-uniform) a segment of a split row: its sums as they are
+      double *dst = partial + static_cast<size_t>(slot) * l_pad;
+      if (sub == 0) {
+#pragma unroll
+        for (int c = 0; c < NCH; c++)
+          if (on[c]) {
+#pragma unroll
+            for (int x = 0; x < 4; x++) dst[4 * (col + 64 * c) + x] = acc[c][x];
+          }
+      }
+      return;
+    }
+  }
+  float4 *dst = reinterpret_cast<float4 *>(
+      slot < 0 ? Y + static_cast<size_t>(row) * l_pad
+               : reinterpret_cast<float *>(partial) + static_cast<size_t>(slot) * l_pad);
   if (sub == 0) {
 #pragma unroll
     for (int c = 0; c < NCH; c++)
       if (on[c])
         dst[col + 64 * c] = make_float4(static_cast<float>(acc[c][0]), static_cast<float>(acc[c][1]),
                                         static_cast<float>(acc[c][2]), static_cast<float>(acc[c][3]));
+  }
+}
+
+// Y[row, :] of split row blockIdx.x = its segments' double partial rows added in segment order, rounded to float32
+// once (tsvd_spmm_reduce_kernel for nmf_spmm_kernel<.., .., double>)
+static __global__ __launch_bounds__(256) void nmf_spmm_reduce_f64_kernel(const int32_t *__restrict__ split_row,
+                                                                         const int32_t *__restrict__ split_first,
+                                                                         const int32_t *__restrict__ split_count,
+                                                                         const double *__restrict__ partial, int l_pad,
+                                                                         float *__restrict__ Y) {
+  const int r = blockIdx.x;
+  const int row = split_row[r], first = split_first[r], count = split_count[r];
+  for (int c = threadIdx.x; c < l_pad; c += 256) {
+    double v = partial[static_cast<size_t>(first) * l_pad + c];
+    for (int k = 1; k < count; k++) v += partial[static_cast<size_t>(first + k) * l_pad + c];
+    Y[static_cast<size_t>(row) * l_pad + c] = static_cast<float>(v);
   }
 }
 

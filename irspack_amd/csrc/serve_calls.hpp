@@ -270,7 +270,7 @@ irs_status irs_serve_recommend_factors(irs_server *sv, int64_t rows, const float
     PhaseClock clock(s);
     upload_padded(sv->user, user_factors, rows, k, KP, s);  // (the user rows)
     serve_run<float>(sv, c, s, clock, [&](int64_t b, int64_t m, float *block) {
-      if (irs_gk_scores_device_(sv->user.ptr + b * KP, sv->item.ptr, KP, m, ni, block, s) != IRS_OK)
+      if (irs_gk_scores_device_(sv->user.ptr + b * KP, sv->item.ptr, KP, m, ni, block, ni, s) != IRS_OK)
         throw std::runtime_error(irs_last_error());
     });
   });

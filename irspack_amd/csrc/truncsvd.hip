@@ -21,6 +21,7 @@
 #include <numeric>
 
 #include "gram_setup.hpp"
+#include "nmf_kernels.hpp"
 #include "tri_inv_kernels.hpp"
 #include "truncsvd_kernels.hpp"
 #include "truncsvd_plan.hpp"
@@ -438,6 +439,65 @@ irs_status irs_truncsvd_stats(irs_truncsvd *t, irs_truncsvd_stats_t *out) {
 
 irs_status irs_truncsvd_destroy(irs_truncsvd *t) {
   return guard([&] { delete t; });
+}
+
+// The fold-in of new rows, z = X V for the item table V [n_items, k] (components_^T): stateless, one sparse x
+// tall-block product with the row sums in double (nmf_spmm_kernel), every element rounded to float32 once - a split
+// row's segments are added in double too.  The sums have a fixed order: the result is a function of the arguments.
+irs_status irs_truncsvd_transform(int64_t rows, int64_t n_items, const int64_t *indptr, const int32_t *indices,
+                                  const float *data, int64_t k, const float *item_factors, int32_t device,
+                                  float *out) {
+  return guard([&] {
+    const int64_t nnz = slim::validate_csr(rows, n_items, indptr, indices, data);
+    check_arg(n_items >= 1, "the matrix must have at least one column.");
+    for (int64_t q = 0; q < nnz; q++) check_arg(std::isfinite(data[q]), "the matrix holds a non-finite value.");
+    check_arg(k >= 1 && k <= tsvd::MAX_L_PAD, "k must lie in 1 .. 576.");
+    check_arg(item_factors != nullptr && (rows == 0 || out != nullptr), "null argument.");
+    check_arg(device >= 0, "irspack_amd: device index out of range.");
+    if (rows == 0) return;
+    require_device(device);
+    hipStream_t s = nullptr;
+    const int64_t k_pad = ceil_div(k, tsvd::RIDGE_NB) * tsvd::RIDGE_NB;
+    const size_t K = static_cast<size_t>(k), KP = static_cast<size_t>(k_pad);
+    tsvd::Csr X;
+    X.rows = rows, X.cols = n_items;
+    std::vector<int32_t> h_ptr(static_cast<size_t>(rows) + 1);
+    for (int64_t i = 0; i <= rows; i++) h_ptr[i] = static_cast<int32_t>(indptr[i]);
+    X.idx.upload(indices, static_cast<size_t>(nnz), s);
+    X.val.upload(data, static_cast<size_t>(nnz), s);
+    tsvd::build_segments(h_ptr, X);
+    DeviceBuffer<float> V, Z;
+    DeviceBuffer<double> partial;
+    V.alloc(static_cast<size_t>(n_items) * KP);
+    if (KP != K) V.zero(s);
+    IRS_HIP(hipMemcpy2DAsync(V.ptr, KP * sizeof(float), item_factors, K * sizeof(float), K * sizeof(float),
+                             static_cast<size_t>(n_items), hipMemcpyHostToDevice, s));
+    Z.alloc(static_cast<size_t>(rows) * KP);
+    partial.alloc(static_cast<size_t>(std::max<int64_t>(1, X.n_slot)) * KP);
+    const int lp = static_cast<int>(k_pad), lvec = lp / 4;
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(ceil_div(X.n_seg, 4))), dim3(256), 0, s,
+                         static_cast<const int32_t *>(X.seg_row.ptr), static_cast<const int32_t *>(X.seg_begin.ptr),
+                         static_cast<const int32_t *>(X.seg_end.ptr), static_cast<const int32_t *>(X.seg_slot.ptr),
+                         static_cast<int>(X.n_seg), static_cast<const int32_t *>(X.idx.ptr),
+                         static_cast<const float *>(X.val.ptr), static_cast<const float *>(V.ptr), lp, Z.ptr,
+                         partial.ptr);
+    };
+    if (lvec == 16) launch(nmf::nmf_spmm_kernel<16, 1, double>);
+    else if (lvec == 32) launch(nmf::nmf_spmm_kernel<32, 1, double>);
+    else if (lvec <= 64) launch(nmf::nmf_spmm_kernel<64, 1, double>);
+    else if (lvec <= 128) launch(nmf::nmf_spmm_kernel<64, 2, double>);
+    else launch(nmf::nmf_spmm_kernel<64, 3, double>);
+    if (X.n_split > 0)
+      hipLaunchKernelGGL(nmf::nmf_spmm_reduce_f64_kernel, dim3(static_cast<unsigned>(X.n_split)), dim3(256), 0, s,
+                         static_cast<const int32_t *>(X.split_row.ptr), static_cast<const int32_t *>(X.split_first.ptr),
+                         static_cast<const int32_t *>(X.split_count.ptr), static_cast<const double *>(partial.ptr), lp,
+                         Z.ptr);
+    IRS_HIP(hipGetLastError());
+    IRS_HIP(hipMemcpy2DAsync(out, K * sizeof(float), Z.ptr, KP * sizeof(float), K * sizeof(float),
+                             static_cast<size_t>(rows), hipMemcpyDeviceToHost, s));
+    IRS_HIP(hipStreamSynchronize(s));
+  });
 }
 
 }  // extern "C"

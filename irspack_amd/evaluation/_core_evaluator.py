@@ -310,31 +310,57 @@ class EvaluatorCore:
         once per cutoff: what ``Evaluator`` does per 128-user block with
         ``model.get_score_block`` (evaluator.py:417-438), without the scores crossing PCIe.
         ``offset``: ground-truth row of user ``begin``.  One ``Metrics`` per cutoff."""
+        return self.get_metrics_similarity_scored(X, W, begin, end, mask, mask_begin, cutoffs, offset,
+                                                  recall_with_cutoff)
+
+    def get_metrics_similarity_scored(self, X: sps.csr_matrix, W: Any, begin: int, end: int,
+                                      mask: Optional["MaskRows"], mask_begin: int, cutoffs: Sequence[int],
+                                      offset: int, recall_with_cutoff: bool = False, *,
+                                      n_scored: Optional[int] = None) -> List[Metrics]:
+        """``get_metrics_similarity`` for a ``W`` that covers the leading ``n_scored`` of the evaluator's columns
+        (``None``: all ``n_items``): the other columns hold ``-inf`` before the block is masked and ranked
+        (``_scored_width``)."""
         if offset < 0 or any(int(c) < 0 for c in cutoffs):
             raise TypeError("cutoff / offset must be non-negative (size_t).")
-        Xc, xp, xi, xd = _lib.csr_arrays(X, np.float64)
+        width = self._scored_width(n_scored)
+        # (the profile rows in their STORAGE order, in which scipy's product adds a row's entries)
+        Xc = X if sps.isspmatrix_csr(X) else sps.csr_matrix(X)
+        xp = np.ascontiguousarray(Xc.indptr, dtype=np.int64)
+        xi = np.ascontiguousarray(Xc.indices, dtype=np.int32)
+        xd = np.ascontiguousarray(Xc.data, dtype=np.float64)
         Wc, wp, wi, wd = _lib.csr_arrays(W, np.float64)  # (a CSC matrix is regrouped into rows here)
-        if Wc.shape != (Xc.shape[1], self.n_items):
-            raise ValueError("W must be X.shape[1] x n_items.")
+        if Wc.shape != (Xc.shape[1], width):
+            raise ValueError("W must be X.shape[1] x n_items." if n_scored is None else
+                             "W must be X.shape[1] x n_scored.")
         rows, nc = end - begin, len(cutoffs)
         cut = np.asarray([int(c) for c in cutoffs], dtype=np.int64)
         sts = (MetricsStruct * max(nc, 1))()
         cnt = np.zeros((max(nc, 1), self.n_items), dtype=np.int64)
         mp, mi = (None, None) if mask is None else mask.rows(mask_begin, mask_begin + rows)
         one_i, one_d = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.float64)
-        check(
-            lib().irs_eval_get_metrics_similarity(
-                self._h, C.c_int64(begin), C.c_int64(end), C.c_int64(Xc.shape[0]), C.c_int64(Xc.shape[1]),
-                ptr(xp, C.c_int64),
-                ptr(xi if xi.size else one_i, C.c_int32), ptr(xd if xd.size else one_d, C.c_double),
-                ptr(wp, C.c_int64), ptr(wi if wi.size else one_i, C.c_int32),
-                ptr(wd if wd.size else one_d, C.c_double),
-                None if mp is None else ptr(mp, C.c_int64), None if mi is None else ptr(mi, C.c_int32),
+        operands = (self._h, C.c_int64(begin), C.c_int64(end), C.c_int64(Xc.shape[0]), C.c_int64(Xc.shape[1]),
+                    ptr(xp, C.c_int64),
+                    ptr(xi if xi.size else one_i, C.c_int32), ptr(xd if xd.size else one_d, C.c_double),
+                    ptr(wp, C.c_int64), ptr(wi if wi.size else one_i, C.c_int32),
+                    ptr(wd if wd.size else one_d, C.c_double))
+        rest = (None if mp is None else ptr(mp, C.c_int64), None if mi is None else ptr(mi, C.c_int32),
                 C.c_int32(nc), ptr(cut, C.c_int64), C.c_int64(offset),
-                C.c_int32(1 if recall_with_cutoff else 0), sts, ptr(cnt, C.c_int64),
-            )
-        )
+                C.c_int32(1 if recall_with_cutoff else 0), sts, ptr(cnt, C.c_int64))
+        if n_scored is None:
+            check(lib().irs_eval_get_metrics_similarity(*operands, *rest))
+        else:
+            check(lib().irs_eval_get_metrics_similarity_scored(*operands, C.c_int64(width), *rest))
         return [Metrics._from_struct(self.n_items, sts[i], cnt[i]) for i in range(nc)]
+
+    def _scored_width(self, n_scored: Optional[int]) -> int:
+        """the columns a model call scores: ``n_items``, or the ``n_scored`` a caller names, ``0 < n_scored <=
+        n_items`` - a model that knows fewer items than the evaluator ranks (``EvaluatorWithColdUser`` with
+        feature-only items): its item operand is ``n_scored`` wide and the columns from there on hold ``-inf``"""
+        if n_scored is None:
+            return self.n_items
+        if isinstance(n_scored, bool) or int(n_scored) != n_scored or not 0 < int(n_scored) <= self.n_items:
+            raise ValueError(f"n_scored must lie in 1 .. n_items={self.n_items}, got {n_scored!r}.")
+        return int(n_scored)
 
     def _call_outputs(self, cutoffs: Sequence[int]):
         nc = len(cutoffs)
@@ -355,15 +381,25 @@ class EvaluatorCore:
         ``offset`` and the result as in ``get_metrics_similarity``; the users' terms are added in the order of
         ``Evaluator``'s block loop at its default ``mb_size`` (128-user chunks merged in sequence), so the float64
         sums are that loop's to the last bit."""
+        return self.get_metrics_dense_similarity_scored(X, W, begin, end, mask, mask_begin, cutoffs, offset,
+                                                        recall_with_cutoff)
+
+    def get_metrics_dense_similarity_scored(self, X: sps.csr_matrix, W: np.ndarray, begin: int, end: int,
+                                            mask: Optional["MaskRows"], mask_begin: int, cutoffs: Sequence[int],
+                                            offset: int, recall_with_cutoff: bool = False, *,
+                                            n_scored: Optional[int] = None) -> List[Metrics]:
+        """``get_metrics_dense_similarity`` for a ``W`` of ``n_scored`` columns, as ``get_metrics_similarity_scored``"""
         if offset < 0 or any(int(c) < 0 for c in cutoffs):
             raise TypeError("cutoff / offset must be non-negative (size_t).")
+        width = self._scored_width(n_scored)
         if not isinstance(W, np.ndarray) or W.ndim != 2 or W.dtype not in (np.dtype("float32"), np.dtype("float64")):
             raise ValueError("W must be a 2-D float32 or float64 ndarray.")
         if not W.flags.c_contiguous:
             raise ValueError("W must be C-contiguous.")
         Xc = X if sps.isspmatrix_csr(X) else sps.csr_matrix(X)
-        if W.shape != (Xc.shape[1], self.n_items):
-            raise ValueError("W must be X.shape[1] x n_items.")
+        if W.shape != (Xc.shape[1], width):
+            raise ValueError("W must be X.shape[1] x n_items." if n_scored is None else
+                             "W must be X.shape[1] x n_scored.")
         xp = np.ascontiguousarray(Xc.indptr, dtype=np.int64)
         xi = np.ascontiguousarray(Xc.indices, dtype=np.int32)
         xd = np.ascontiguousarray(Xc.data, dtype=np.float64)
@@ -371,15 +407,15 @@ class EvaluatorCore:
         nc, cut, sts, cnt = self._call_outputs(cutoffs)
         mp, mi = (None, None) if mask is None else mask.rows(mask_begin, mask_begin + rows)
         one_i, one_d = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.float64)
-        check(
-            lib().irs_eval_get_metrics_dense_similarity(
-                self._h, begin, end, Xc.shape[0], Xc.shape[1], ptr(xp, C.c_int64),
-                ptr(xi if xi.size else one_i, C.c_int32), ptr(xd if xd.size else one_d, C.c_double),
-                1 if W.dtype == np.float64 else 0, W.ctypes.data_as(C.c_void_p),
-                None if mp is None else ptr(mp, C.c_int64), None if mi is None else ptr(mi, C.c_int32),
-                nc, ptr(cut, C.c_int64), offset, 1 if recall_with_cutoff else 0, sts, ptr(cnt, C.c_int64),
-            )
-        )
+        operands = (self._h, begin, end, Xc.shape[0], Xc.shape[1], ptr(xp, C.c_int64),
+                    ptr(xi if xi.size else one_i, C.c_int32), ptr(xd if xd.size else one_d, C.c_double),
+                    1 if W.dtype == np.float64 else 0, W.ctypes.data_as(C.c_void_p))
+        rest = (None if mp is None else ptr(mp, C.c_int64), None if mi is None else ptr(mi, C.c_int32),
+                nc, ptr(cut, C.c_int64), offset, 1 if recall_with_cutoff else 0, sts, ptr(cnt, C.c_int64))
+        if n_scored is None:
+            check(lib().irs_eval_get_metrics_dense_similarity(*operands, *rest))
+        else:
+            check(lib().irs_eval_get_metrics_dense_similarity_scored(*operands, width, *rest))
         return [Metrics._from_struct(self.n_items, sts[i], cnt[i]) for i in range(nc)]
 
     def get_metrics_factors(self, user_factors: np.ndarray, item_factors: np.ndarray, begin: int, end: int,
@@ -391,14 +427,30 @@ class EvaluatorCore:
         576``), masked and ranked once per cutoff without the scores crossing PCIe.  Mask, cutoffs, ``offset``
         and the result as in ``get_metrics_similarity``; the sums in the order of the default block loop, as in
         ``get_metrics_dense_similarity``."""
+        return self.get_metrics_factors_scored(user_factors, item_factors, begin, end, mask, mask_begin, cutoffs,
+                                               offset, recall_with_cutoff)
+
+    def get_metrics_factors_scored(self, user_factors: np.ndarray, item_factors: np.ndarray, begin: int, end: int,
+                                   mask: Optional["MaskRows"], mask_begin: int, cutoffs: Sequence[int],
+                                   offset: int, recall_with_cutoff: bool = False, *, n_scored: Optional[int] = None,
+                                   running: Optional[Sequence[Metrics]] = None) -> List[Metrics]:
+        """``get_metrics_factors`` for an ``item_factors`` of ``n_scored`` rows, as
+        ``get_metrics_similarity_scored``.  ``running`` (one ``Metrics`` per cutoff): what earlier calls returned for
+        the users before these; the call merges its 128-user chunks onto those sums on the device and returns the
+        continued totals, item counts included - users handed over in several calls of whole chunks (one fold-in
+        each) are then summed exactly as one call sums them."""
         if offset < 0 or any(int(c) < 0 for c in cutoffs):
             raise TypeError("cutoff / offset must be non-negative (size_t).")
+        width = self._scored_width(n_scored)
+        if running is not None and len(running) != len(cutoffs):
+            raise ValueError("running must hold one Metrics per cutoff.")
         for name, F in (("user_factors", user_factors), ("item_factors", item_factors)):
             if not isinstance(F, np.ndarray) or F.ndim != 2:
                 raise ValueError(f"{name} must be a 2-D ndarray.")
         k = user_factors.shape[1]
-        if item_factors.shape != (self.n_items, k):
-            raise ValueError("item_factors must be n_items x user_factors.shape[1].")
+        if item_factors.shape != (width, k):
+            raise ValueError("item_factors must be n_items x user_factors.shape[1]." if n_scored is None else
+                             "item_factors must be n_scored x user_factors.shape[1].")
         if not 1 <= k <= 576:
             raise ValueError("the number of factors must lie in 1 .. 576.")
         U = np.ascontiguousarray(user_factors, dtype=np.float32)
@@ -406,14 +458,24 @@ class EvaluatorCore:
         rows = end - begin
         nc, cut, sts, cnt = self._call_outputs(cutoffs)
         mp, mi = (None, None) if mask is None else mask.rows(mask_begin, mask_begin + rows)
-        check(
-            lib().irs_eval_get_metrics_factors(
-                self._h, begin, end, U.shape[0], k, ptr(U, C.c_float), ptr(V, C.c_float),
-                None if mp is None else ptr(mp, C.c_int64), None if mi is None else ptr(mi, C.c_int32),
-                nc, ptr(cut, C.c_int64), offset, 1 if recall_with_cutoff else 0, sts, ptr(cnt, C.c_int64),
-            )
-        )
-        return [Metrics._from_struct(self.n_items, sts[i], cnt[i]) for i in range(nc)]
+        operands = (self._h, begin, end, U.shape[0], k, ptr(U, C.c_float), ptr(V, C.c_float))
+        rest = (None if mp is None else ptr(mp, C.c_int64), None if mi is None else ptr(mi, C.c_int32),
+                nc, ptr(cut, C.c_int64), offset, 1 if recall_with_cutoff else 0, sts, ptr(cnt, C.c_int64))
+        if n_scored is None and running is None:
+            check(lib().irs_eval_get_metrics_factors(*operands, *rest))
+        else:
+            before = None
+            if running is not None:
+                before = (MetricsStruct * max(nc, 1))()
+                for st, m in zip(before, running):
+                    st.valid_user, st.total_user = m.valid_user, m.total_user
+                    st.hit, st.recall, st.ndcg, st.precision, st.map = m.hit, m.recall, m.ndcg, m.precision, m.map
+            check(lib().irs_eval_get_metrics_factors_scored(*operands, width, before, *rest))
+        out = [Metrics._from_struct(self.n_items, sts[i], cnt[i]) for i in range(nc)]
+        if running is not None:
+            for m, earlier in zip(out, running):
+                m.item_cnt = m.item_cnt + earlier.item_cnt
+        return out
 
     def last_call_phases(self) -> Dict[str, float]:
         """Stream time in milliseconds of the last ``get_metrics_dense_similarity`` / ``get_metrics_factors``

@@ -11,7 +11,7 @@ once per cutoff and merges the ``Metrics``; at the end it checks that the blocks
 user and adds ``catalog_coverage``.  The fused path (an ``irspack_amd`` iALS model on the
 evaluator's device) bypasses blocks altogether.
 
-Two things are done differently from the reference's Python, with the same results:
+Three things are done differently from the reference's Python, with the same results:
 
 * A host score block is masked ON THE DEVICE: ``EvaluatorCore.get_metrics_masked`` uploads the
   block once (the upload is the copy the reference makes before masking, :387), sets the mask's
@@ -24,6 +24,9 @@ Two things are done differently from the reference's Python, with the same resul
   other recommenders of this package are scored on the device as well (``_device_path``): similarity models
   with sparse weights, dense item weights (EASE, EDLAE) and factor models (truncated SVD, NMF);
   tests/test_gpu_evaluator_models.py.
+* ``EvaluatorWithColdUser`` does the same for users the model has not seen (``cold_user_operands``): the fold-in
+  of a factor model, the scores, the mask and the ranking run on the device, and the feature-only items a model
+  cannot score are columns of ``-inf`` written there; tests/test_gpu_evaluator_cold.py.
 """
 
 import enum
@@ -408,17 +411,143 @@ class Evaluator:
         return acc.results()
 
 
+class ColdUserOperands:
+    """What ``cold_user_operands`` found: how the device scores a model's cold users.
+
+    ``kind``      ``"similarity"`` / ``"dense_similarity"``: score = ``profiles[u] @ weights``;
+                  ``"factors"``: score = ``fold_in(rows) @ item_table().T`` in float32
+    ``n_scored``  the leading columns of the evaluator that the model scores (the others stay ``-inf``)
+    ``profiles``  the users' rows as CSR float64 in their storage order (similarity kinds)
+    ``weights``   the model's ``W`` as it is (similarity kinds)
+    ``fold_in``   ``CSR rows -> (rows, k) float32`` user factors, device work (factor kind)
+    ``item_table``  ``() -> (n_scored, k) float32`` C-contiguous item factors, made when called (factor kind)"""
+
+    def __init__(self, kind: str, n_scored: int, profiles: Any = None, weights: Any = None, fold_in: Any = None,
+                 item_table: Any = None) -> None:
+        self.kind, self.n_scored, self.profiles, self.weights = kind, n_scored, profiles, weights
+        self.fold_in, self.item_table = fold_in, item_table
+
+
+def _own(model: Any, cls: type, *names: str) -> bool:
+    """whether the model's class scores with the package class's own methods (nothing overrides them)"""
+    return all(getattr(type(model), name, None) is getattr(cls, name) for name in names)
+
+
+def _float32_valued(X: sps.csr_matrix) -> bool:
+    return X.dtype == np.float32 or bool(np.array_equal(X.data.astype(np.float32).astype(X.dtype), X.data))
+
+
+def cold_user_operands(model: Any, input_interaction: Any, cold_item_features: Optional[Any] = None,
+                       ) -> Optional[ColdUserOperands]:
+    """How the device can score ``model.get_score_cold_user(input_interaction)`` - or, with ``cold_item_features``
+    and a feature-aware iALS model, its item-feature scorer -, or ``None`` when only the model's own host code can
+    (``EvaluatorWithColdUser`` then walks its block loop).  Host only: nothing here opens the device; a factor
+    model's fold-in and item table are returned as callables.
+
+    Recognised, each through its class's OWN ``get_score_cold_user`` (a subclass that overrides it is ``None``):
+    ``BaseSimilarityRecommender`` with a sparse ``W`` (``"similarity"``) or a dense C-contiguous ``W``
+    (``"dense_similarity"``) - only when the host product is computed in float64, that is with float32 / float64
+    operands of which at least one is float64, because only then is the device product the host's bit for bit -;
+    trained ``IALSRecommender`` (its ``_create_cold_user_with_item_features_scorer`` its own too),
+    ``TruncatedSVDRecommender``, ``NMFRecommender`` and trained ``MultVAERecommender`` (``"factors"``, ``1 <= k <=
+    576``).  A profile row that stores a column twice is ``None`` as well (two lanes of the sparse kernel would
+    add to one sum at once; the fold-ins want canonical rows)."""
+    from ..recommenders.base import BaseSimilarityRecommender
+    from ..recommenders.ials import IALSRecommender
+    from ..recommenders.multvae import MultVAERecommender
+    from ..recommenders.nmf import NMFModel, NMFRecommender
+    from ..recommenders.truncsvd import TruncatedSVDDecomposer, TruncatedSVDRecommender
+    from ..serving import _has_duplicate_columns
+
+    if not sps.issparse(input_interaction) or input_interaction.dtype not in _SCORE_DTYPES:
+        return None
+    X = input_interaction if sps.isspmatrix_csr(input_interaction) else sps.csr_matrix(input_interaction)
+    n_warm = X.shape[1]
+    if getattr(model, "n_items", None) != n_warm or _has_duplicate_columns(X):
+        return None
+    if isinstance(model, BaseSimilarityRecommender):
+        W = getattr(model, "_W", None)
+        if not _own(model, BaseSimilarityRecommender, "get_score_cold_user") or W is None or \
+                getattr(W, "shape", None) != (n_warm, n_warm) or W.dtype not in _SCORE_DTYPES or \
+                np.result_type(X.dtype, W.dtype) != np.float64:
+            return None
+        if sps.issparse(W):
+            kind = "similarity"
+        elif isinstance(W, np.ndarray) and W.flags.c_contiguous:
+            kind = "dense_similarity"
+        else:
+            return None
+        return ColdUserOperands(kind, n_warm, profiles=X if X.dtype == np.float64 else X.astype(np.float64), weights=W)
+
+    def factors(fold_in: Any, item_table: Any, k: Any, n_scored: int = n_warm) -> Optional[ColdUserOperands]:
+        if not isinstance(k, (int, np.integer)) or not 1 <= k <= 576:
+            return None
+        return ColdUserOperands("factors", n_scored, fold_in=fold_in, item_table=item_table)
+
+    def table_of(F: Any) -> Any:
+        return lambda: np.ascontiguousarray(F, dtype=np.float32)
+
+    if isinstance(model, IALSRecommender):
+        if not _own(model, IALSRecommender, "get_score_cold_user", "_create_cold_user_with_item_features_scorer") or \
+                getattr(model, "trainer", None) is None:
+            return None
+        n_cold = 0 if cold_item_features is None else cold_item_features.shape[0]
+        if n_cold and model.item_features is not None:
+            # the item-feature scorer (ials.py:493-517): the feature-only items' embeddings below the trained ones
+            def item_table() -> np.ndarray:
+                return np.ascontiguousarray(np.concatenate(
+                    [model.get_item_embedding(), model.compute_item_embedding_from_features(cold_item_features)],
+                    axis=0), dtype=np.float32)
+            return factors(model.compute_user_embedding, item_table, model.n_components, n_warm + n_cold)
+        return factors(model.compute_user_embedding,
+                       lambda: np.ascontiguousarray(model.get_item_embedding(), dtype=np.float32), model.n_components)
+    if isinstance(model, TruncatedSVDRecommender):
+        from ..utils import truncated_svd_transform
+
+        dec = getattr(model, "decomposer_", None)
+        C_ = getattr(dec, "components_", None)
+        if not _own(model, TruncatedSVDRecommender, "get_score_cold_user") or type(dec) is not TruncatedSVDDecomposer \
+                or not isinstance(C_, np.ndarray) or C_.ndim != 2 or C_.dtype != np.float32 or C_.shape[1] != n_warm \
+                or not _float32_valued(X):  # (the device fold-in reads the profile values as float32)
+            return None
+        return factors(lambda rows: truncated_svd_transform(rows, C_), table_of(C_.T), C_.shape[0])
+    if isinstance(model, NMFRecommender):
+        nmf, H = getattr(model, "nmf_model", None), getattr(model, "H", None)
+        if not _own(model, NMFRecommender, "get_score_cold_user") or type(nmf) is not NMFModel or \
+                not isinstance(H, np.ndarray) or H.ndim != 2 or H.dtype != np.float32 or H.shape[1] != n_warm:
+            return None
+        return factors(nmf.transform, table_of(H.T), H.shape[0])
+    if isinstance(model, MultVAERecommender):
+        if not _own(model, MultVAERecommender, "get_score_cold_user", "profile_factors", "factor_tables") or \
+                getattr(model, "trainer", None) is None:
+            return None
+        hidden = model.trainer.hyper["dec_hidden_dim"] + 2  # [h2 | 1 | -lse] @ [W4; b4; 1]
+        return factors(model.profile_factors,
+                       lambda: np.ascontiguousarray(model.factor_tables()[1].T, dtype=np.float32), hidden)
+    return None
+
+
 class EvaluatorWithColdUser(Evaluator):
     """evaluator.py:444-657: evaluates against users the model has not seen, whose known
     interactions are ``input_interaction``; ``cold_item_features`` adds feature-only items as
-    extra columns behind the training items."""
+    extra columns behind the training items.
+
+    With ``fused=True`` (the default) a model that ``cold_user_operands`` recognises is folded in, scored, masked
+    and ranked on the device (``_device_path``); any other model, and every model with ``fused=False``, goes
+    through the block loop: its own host scores ``mb_size`` users at a time, masked and ranked on the device."""
+
+    #: users per fold-in of a factor model: whole 128-user chunks of the host loop, bounded by the fold-in's
+    #: memory - the NMF transform keeps three ``rows x k_pad`` float32 blocks (W, XH and the copy that comes
+    #: home), 226 MB at ``k_pad = 576``, the largest of the four fold-ins per row
+    fold_in_rows = 32768
 
     def __init__(self, input_interaction: Any, ground_truth: Any, cutoff: int = 10,
                  target_metric: str = "ndcg", recommendable_items: Optional[List[int]] = None,
                  per_user_recommendable_items: Union[None, List[List[int]], Any] = None,
                  masked_interactions: Optional[Any] = None, n_threads: Optional[int] = None,
                  recall_with_cutoff: bool = False, mb_size: int = 1024,
-                 cold_item_features: Optional[Any] = None, device: Optional[int] = None) -> None:
+                 cold_item_features: Optional[Any] = None, device: Optional[int] = None,
+                 fused: bool = True) -> None:
         if input_interaction.shape[0] != ground_truth.shape[0]:
             raise ValueError("input_interaction and ground_truth must have the same number of rows.")
         n_warm = input_interaction.shape[1]
@@ -434,7 +563,7 @@ class EvaluatorWithColdUser(Evaluator):
                          recommendable_items=recommendable_items,
                          per_user_recommendable_items=per_user_recommendable_items,
                          masked_interactions=masked_interactions, n_threads=n_threads,
-                         recall_with_cutoff=recall_with_cutoff, mb_size=mb_size, fused=False,
+                         recall_with_cutoff=recall_with_cutoff, mb_size=mb_size, fused=fused,
                          device=device)
         self.input_interaction = input_interaction
         self.cold_item_features = cold_item_features
@@ -486,10 +615,59 @@ class EvaluatorWithColdUser(Evaluator):
             block = np.ascontiguousarray(block, dtype=np.float64)
         return block
 
+    def _cold_operands(self, model: Any) -> Optional[ColdUserOperands]:
+        return cold_user_operands(model, self.input_interaction, self.cold_item_features) if self.fused else None
+
+    def _device_path(self, model: Any) -> str:
+        """which way ``_evaluate_model`` takes for ``model``: ``"similarity"``, ``"dense_similarity"`` or
+        ``"factors"`` - fold-in, scores, mask and ranking on the device, only with ``fused`` - or ``"blocks"`` (the
+        model's host scores, ranked block by block)"""
+        found = self._cold_operands(model)
+        return "blocks" if found is None else found.kind
+
+    def _sparse_weight_rows(self, W: Any) -> sps.csr_matrix:
+        """a sparse ``W`` by rows in float64 (float32 is cast exactly: the host product with a float64 operand is
+        computed in float64 anyway), kept while calls pass the same object"""
+        held = getattr(self, "_cold_rows_held", None)
+        if held is None or held[0] is not W:
+            Wr = W if sps.isspmatrix_csr(W) else sps.csr_matrix(W)
+            if Wr.dtype != np.float64:
+                Wr = Wr.astype(np.float64)
+            elif Wr is W and not W.has_sorted_indices:
+                Wr = W.copy()  # (the model's matrix stays as it is)
+            Wr.sort_indices()
+            held = self._cold_rows_held = (W, Wr)
+        return held[1]
+
+    def _evaluate_on_device(self, found: ColdUserOperands, cutoffs: List[int]) -> List[Dict[str, float]]:
+        mask = self._mask_rows(self._score_matrix_mask())
+        rwc, n = self.recall_with_cutoff, self.n_users
+        if found.kind == "similarity":
+            ranked = self.core.get_metrics_similarity_scored(found.profiles, self._sparse_weight_rows(found.weights), 0,
+                                                             n, mask, 0, cutoffs, 0, rwc, n_scored=found.n_scored)
+        elif found.kind == "dense_similarity":
+            ranked = self.core.get_metrics_dense_similarity_scored(found.profiles, found.weights, 0, n, mask, 0, cutoffs,
+                                                                   0, rwc, n_scored=found.n_scored)
+        else:
+            # a fold-in per `fold_in_rows` users (whole chunks of the host loop); the folded-in table comes home and
+            # goes up again with its call, which continues the sums of the calls before it
+            step = max(128, self.fold_in_rows // 128 * 128)
+            items = found.item_table()
+            ranked = [Metrics(self.n_items) for _ in cutoffs]
+            for b in range(0, n, step):
+                e = min(b + step, n)
+                users = np.ascontiguousarray(found.fold_in(self.input_interaction[b:e]), dtype=np.float32)
+                ranked = self.core.get_metrics_factors_scored(users, items, 0, e - b, mask, b, cutoffs, b, rwc,
+                                                              n_scored=found.n_scored, running=ranked)
+        return [self._with_coverage(m) for m in ranked]
+
     def _evaluate_model(self, model: Any, cutoffs: List[int]) -> List[Dict[str, float]]:
         if model.n_items != self.n_warm_items:
             raise ValueError("The model and input_interaction assume different numbers of "
                              "training items.")
+        found = self._cold_operands(model)
+        if found is not None:
+            return self._evaluate_on_device(found, cutoffs)
         acc = _BlockAccumulator(self, cutoffs, self._mask_rows(self._score_matrix_mask()))
         score = self._cold_user_scorer(model)
         for b in range(0, self.n_users, self.mb_size):

@@ -343,6 +343,40 @@ def truncated_svd(X, n_components: int, random_seed: int = 0, *, n_iter: int = 5
     return z, sigma, comps
 
 
+def truncated_svd_transform(X, components: np.ndarray, *, device: Optional[int] = None) -> np.ndarray:
+    """The fold-in of the truncated SVD for rows the fit has not seen, ``X @ components.T`` (what
+    ``TruncatedSVD.transform`` computes), on the device (``irs_truncsvd_transform``): ``components`` is ``(k, I)``
+    float32 with ``1 <= k <= 576``, the result ``(rows, k)`` float32.  The values of ``X`` are read as float32 and
+    the entries of a row are taken in column order with duplicates summed; every row sum is kept in double and
+    rounded to float32 once, so an element differs from the float64 product by one float32 rounding plus the
+    error of a double sum.  The result depends on the arguments alone: two calls give identical bytes."""
+    C_ = np.asarray(components)
+    if C_.ndim != 2 or C_.dtype != np.float32:
+        raise ValueError("components must be a 2-D float32 array (k, n_items).")
+    k, n_items = C_.shape
+    if not 1 <= k <= 576:
+        raise ValueError("the number of components must lie in 1 .. 576.")
+    Xc = sps.csr_matrix(X, dtype=np.float32)
+    if Xc.shape[1] != n_items:
+        raise ValueError(f"X has {Xc.shape[1]} columns, components has {n_items}.")
+    if not Xc.has_canonical_format:
+        Xc = Xc.copy()
+        Xc.sum_duplicates()  # (the C call wants sorted rows without duplicates)
+    out = np.zeros((Xc.shape[0], k), dtype=np.float32)
+    if Xc.shape[0] == 0:
+        return out
+    table = np.ascontiguousarray(C_.T)  # (I, k): a gathered row is contiguous
+    indptr = np.ascontiguousarray(Xc.indptr, dtype=np.int64)
+    indices = np.ascontiguousarray(Xc.indices, dtype=np.int32)
+    data = np.ascontiguousarray(Xc.data, dtype=np.float32)
+    if data.size == 0:
+        indices, data = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.float32)
+    check(lib().irs_truncsvd_transform(Xc.shape[0], n_items, ptr(indptr, C.c_int64), ptr(indices, C.c_int32),
+                                       ptr(data, C.c_float), k, ptr(table, C.c_float),
+                                       _lib.default_device() if device is None else device, ptr(out, C.c_float)))
+    return out
+
+
 class ConvergenceWarning(UserWarning):
     """scikit-learn's ``sklearn.exceptions.ConvergenceWarning`` by name (this package does not import scikit-learn)"""
 
