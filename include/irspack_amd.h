@@ -744,6 +744,57 @@ irs_status irs_bpr_set_state(irs_bpr *t, const float *U, const float *V, const f
 irs_status irs_bpr_stats(irs_bpr *t, irs_bpr_stats_t *out);
 irs_status irs_bpr_destroy(irs_bpr *t);
 
+/* The WARP loss on the same handle type ("WARP"; the project's own synchronous form, not
+ * LightFM bit parity).  State, start, positives, position space and the order of an epoch are those of the BPR
+ * handle: position p of epoch e is the (u, i) that a handle of irs_bpr_create with the same seed gives.
+ *   candidates  candidate t (1 <= t <= max_sampled <= 256) of position p is the r-th item its user has no positive
+ *               on, r from one hash of (seed, epoch, p * 256 + t) under a key of the epoch of its own; it does not
+ *               depend on max_sampled.
+ *   search      every position reads the parameters as the batch found them: x+ = U[u].V[i] + b[i]; for t = 1, 2,
+ *               ...: x- = U[u].V[j_t] + b[j_t]; the first t with x- > x+ - 1 ends the search with j = j_t.  A
+ *               position without such a t contributes nothing and touches no row.
+ *   weight      w_t = min(ln(max(1, floor((n_items - 1) / t))), 10), computed once on the host in double.
+ *   update      that of irs_bpr_run_epochs with w_t in place of the sigmoid; L2 term and Adagrad are unchanged.
+ *               The fixed-point scale is 2^s, s = 62 - (ceil(log2 n) + 14), at most 40.
+ *   create_warp       the arguments of irs_bpr_create and max_sampled.  run_epochs, get_state, set_state, stats and
+ *                     destroy work on its handle; irs_bpr_sample and irs_bpr_step_triples return
+ *                     IRS_INVALID_ARGUMENT.  The calls below return IRS_INVALID_ARGUMENT on a handle of
+ *                     irs_bpr_create.
+ *   warp_candidates   positions [first, first + count) of `epoch`: users, pos [count], cand [count, max_sampled].
+ *   warp_search       the search on the current state with the caller's candidates (cand [n, max_sampled]);
+ *                     nothing is updated.  neg_out [n]: j, or -1 without a violation; tries_out [n]: the
+ *                     candidates examined (max_sampled without a violation).
+ *   warp_step         one synchronous batch on the caller's positions and candidates.
+ *   warp_stats        see the struct.
+ * IRS_INVALID_ARGUMENT, before any device work: max_sampled outside [1, 256], a null array, a user, an item or a
+ * candidate out of range, n * max_sampled >= 2^31, a window outside the epoch. */
+typedef struct {
+  int32_t max_sampled;
+  int32_t scale_log2;       /* s of a full batch */
+  int32_t in_flight;        /* candidate rows the search gathers at a time (IRSPACK_AMD_WARP_IN_FLIGHT) */
+  int32_t reserved;
+  int64_t epoch_positions;  /* the last epoch run_epochs ran: its positions, ... */
+  int64_t epoch_updates;    /* ... those that found a violation, ... */
+  int64_t epoch_tries;      /* ... and the candidates examined, summed */
+  int64_t call_positions;   /* the same of the last run_epochs (its last epoch), warp_search or warp_step call */
+  int64_t call_updates;
+  int64_t call_tries;
+  double epoch_ms;          /* as in irs_bpr_stats_t */
+  double search_ms;         /* the search-and-gradient launches (IRSPACK_AMD_BPR_PHASES=1), else 0 */
+  double apply_ms;
+} irs_bpr_warp_stats_t;
+irs_status irs_bpr_create_warp(int64_t n_users, int64_t n_items, const int64_t *indptr, const int32_t *indices,
+                               const float *data, int32_t k, float user_alpha, float item_alpha, float learning_rate,
+                               int64_t batch_size, uint64_t seed, const float *user_init /* may be NULL */,
+                               const float *item_init /* may be NULL */, int32_t device, int32_t max_sampled,
+                               irs_bpr **out);
+irs_status irs_bpr_warp_candidates(irs_bpr *t, int64_t epoch, int64_t first, int64_t count, int32_t *users,
+                                   int32_t *pos, int32_t *cand);
+irs_status irs_bpr_warp_search(irs_bpr *t, int64_t n, const int32_t *users, const int32_t *pos, const int32_t *cand,
+                               int32_t *neg_out, int32_t *tries_out);
+irs_status irs_bpr_warp_step(irs_bpr *t, int64_t n, const int32_t *users, const int32_t *pos, const int32_t *cand);
+irs_status irs_bpr_warp_stats(irs_bpr *t, irs_bpr_warp_stats_t *out);
+
 /* ------------------------------------------------------------------ Mult-VAE
  * MultVAERecommender (src/irspack/recommenders/multvae.py; the reference trains with jax / haiku / optax and jax's
  * generator - the trainer here is this library's own statement of the same model).

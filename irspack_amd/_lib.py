@@ -137,6 +137,24 @@ class BprStatsStruct(C.Structure):  # irs_bpr_stats_t
     ]
 
 
+class BprWarpStatsStruct(C.Structure):  # irs_bpr_warp_stats_t
+    _fields_ = [
+        ("max_sampled", C.c_int32),
+        ("scale_log2", C.c_int32),
+        ("in_flight", C.c_int32),
+        ("reserved", C.c_int32),
+        ("epoch_positions", C.c_int64),
+        ("epoch_updates", C.c_int64),
+        ("epoch_tries", C.c_int64),
+        ("call_positions", C.c_int64),
+        ("call_updates", C.c_int64),
+        ("call_tries", C.c_int64),
+        ("epoch_ms", C.c_double),
+        ("search_ms", C.c_double),
+        ("apply_ms", C.c_double),
+    ]
+
+
 class MultVaeStatsStruct(C.Structure):  # irs_multvae_stats_t
     _fields_ = [
         ("n_updates", C.c_int64),
@@ -243,6 +261,11 @@ EXPORTED_SYMBOLS = [
     "irs_bpr_set_state",
     "irs_bpr_stats",
     "irs_bpr_destroy",
+    "irs_bpr_create_warp",
+    "irs_bpr_warp_candidates",
+    "irs_bpr_warp_search",
+    "irs_bpr_warp_step",
+    "irs_bpr_warp_stats",
     "irs_multvae_create",
     "irs_multvae_run_epochs",
     "irs_multvae_order",
@@ -319,6 +342,14 @@ ARGTYPES = {
     "irs_bpr_set_state": [C.c_void_p] + [C.POINTER(C.c_float)] * 6 + [C.c_int64],
     "irs_bpr_stats": [C.c_void_p, C.c_void_p],
     "irs_bpr_destroy": [C.c_void_p],
+    "irs_bpr_create_warp": [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                            C.c_int32, C.c_float, C.c_float, C.c_float, C.c_int64, C.c_uint64, C.POINTER(C.c_float),
+                            C.POINTER(C.c_float), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)],
+    "irs_bpr_warp_candidates": [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32),
+                                C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+    "irs_bpr_warp_search": [C.c_void_p, C.c_int64] + [C.POINTER(C.c_int32)] * 5,
+    "irs_bpr_warp_step": [C.c_void_p, C.c_int64] + [C.POINTER(C.c_int32)] * 3,
+    "irs_bpr_warp_stats": [C.c_void_p, C.c_void_p],
     "irs_multvae_create": [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float),
                            C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_double, C.c_int64, C.c_int64,
                            C.c_float, C.c_uint64, C.POINTER(C.POINTER(C.c_float)), C.c_int32, C.POINTER(C.c_void_p)],

@@ -1,8 +1,10 @@
 // Host-only part of the BPR trainer (bpr.hip): argument checks, the filter of the positives, the per-entry
 // arrays of the sampler, the counter-based generator with its permutation and unseen-rank mapping (shared with
-// the kernels through IRS_BPR_HD) and the fixed-point scale of the gradient sums.  No HIP in it: it compiles
-// with the host compiler alone (tests/host/bpr_host_prep_main.cpp).  DESIGN.md section 14.
+// the kernels through IRS_BPR_HD), the fixed-point scale of the gradient sums, and what the WARP loss adds to these
+// (its candidate stream, weight table, scale and checks).  No HIP in it: it compiles with the host compiler alone
+// (tests/host/bpr_host_prep_main.cpp, warp_host_prep_main.cpp).  DESIGN.md section 14.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <vector>
@@ -212,6 +214,75 @@ inline int scale_log2(int64_t n) {
   while ((int64_t(1) << lg) < n) lg++;
   const int s = 62 - (lg + 2 + PARAM_CAP_LOG2);
   return s < MAX_SCALE_LOG2 ? s : MAX_SCALE_LOG2;
+}
+
+// ---- WARP (loss "warp": DESIGN.md section 14, "WARP") ---------------------------------------------------------
+constexpr int WARP_MAX_SAMPLED = 256;  // candidate t of position p draws from counter p * 256 + t, 1 <= t <= 256
+constexpr double WARP_MAX_LOSS = 10.0;       // LightFM's MAX_LOSS
+constexpr int WARP_WEIGHT_LOG2 = 4;          // every weight is <= 10 < 2^4
+constexpr int WARP_MAX_SCALE_LOG2 = 40;      // 2^4 2 PARAM_CAP 2^40 = 2^53: every scaled contribution is an exact double
+
+// The key of an epoch's candidate stream.  epoch_key's streams enter as 2 epoch + stream, so a third stream there
+// would be the order key of the next epoch; this derivation shares no counter with it.
+IRS_BPR_HD uint64_t warp_key(uint64_t seed, int64_t epoch) {
+  return mix64(mix64(seed) ^ mix64(mix64(static_cast<uint64_t>(epoch)) + 0xD1B54A32D192ED03ull));
+}
+
+// candidate t (from 1) of a position whose user has the sorted row s[0 .. deg): it does not depend on max_sampled
+IRS_BPR_HD int32_t warp_candidate(uint64_t key, uint64_t position, int32_t t, const int32_t *s, int32_t deg,
+                                  int32_t n_items) {
+  const uint32_t r = draw_rank(key, position * WARP_MAX_SAMPLED + static_cast<uint64_t>(t),
+                               static_cast<uint32_t>(n_items - deg));
+  return unseen_by_rank(s, deg, static_cast<int32_t>(r));
+}
+
+// (u, i) of a position and its first `count` candidates on the host, as the kernels compute them
+inline void warp_candidates_one(const Positives &p, int64_t n_items, const Perm &perm, uint64_t key, int64_t position,
+                                int32_t count, int32_t *u, int32_t *i, int32_t *cand) {
+  const uint32_t e = permute(perm, static_cast<uint32_t>(position));
+  *u = p.pos_user[e], *i = p.pos_item[e];
+  const int32_t b = p.indptr[*u], deg = p.indptr[*u + 1] - b;
+  for (int32_t t = 1; t <= count; t++)
+    cand[t - 1] = warp_candidate(key, static_cast<uint64_t>(position), t, p.indices.data() + b, deg,
+                                 static_cast<int32_t>(n_items));
+}
+
+// w_t = min(ln(max(1, floor((n_items - 1) / t))), 10), t = 1 .. max_sampled: LightFM's rank estimate when the first
+// violation is found at try t, in double, once per handle (the device needs no log; the restatement uses the same)
+inline std::vector<double> warp_weights(int64_t n_items, int32_t max_sampled) {
+  std::vector<double> w(static_cast<size_t>(max_sampled));
+  for (int32_t t = 1; t <= max_sampled; t++) {
+    const int64_t rank = (n_items - 1) / t;
+    w[t - 1] = std::min(std::log(static_cast<double>(rank < 1 ? 1 : rank)), WARP_MAX_LOSS);
+  }
+  return w;
+}
+
+// the scale of a WARP batch: a contribution is bounded by 2^4 2 PARAM_CAP instead of 2 PARAM_CAP
+inline int warp_scale_log2(int64_t n) {
+  int lg = 0;
+  while ((int64_t(1) << lg) < n) lg++;
+  const int s = 62 - (lg + 2 + PARAM_CAP_LOG2 + WARP_WEIGHT_LOG2);
+  return s < WARP_MAX_SCALE_LOG2 ? s : WARP_MAX_SCALE_LOG2;
+}
+
+inline void validate_max_sampled(int32_t max_sampled) {
+  check_arg(max_sampled >= 1, "max_sampled must be >= 1.");
+  check_arg(max_sampled <= WARP_MAX_SAMPLED, "max_sampled must be <= 256.");
+}
+
+// positions with the caller's candidates: cand is n x max_sampled, row-major
+inline void validate_warp_batch(int64_t n, const int32_t *users, const int32_t *pos, const int32_t *cand,
+                                int32_t max_sampled, int64_t n_users, int64_t n_items) {
+  check_arg(n >= 0, "n must be >= 0.");
+  check_arg(n * max_sampled < (int64_t(1) << 31), "n * max_sampled must be below 2^31.");
+  check_arg(n == 0 || (users && pos && cand), "the position and candidate arrays must not be null.");
+  for (int64_t q = 0; q < n; q++) {
+    check_arg(users[q] >= 0 && users[q] < n_users, "a position's user is out of range.");
+    check_arg(pos[q] >= 0 && pos[q] < n_items, "a position's item is out of range.");
+    for (int64_t c = q * max_sampled; c < (q + 1) * max_sampled; c++)
+      check_arg(cand[c] >= 0 && cand[c] < n_items, "a candidate is out of range.");
+  }
 }
 
 // lanes that serve one triple (and one row of the apply kernel): one float4 per lane up to a whole wave

@@ -3,7 +3,7 @@ the recommenders whose compiled core is rebuilt here."""
 
 from .base import BaseRecommender, BaseSimilarityRecommender, BaseUserSimilarityRecommender
 from .base_earlystop import BaseRecommenderWithEarlyStopping
-from .bpr import BPRFMRecommender
+from .bpr import BPRFMRecommender, WARPFMRecommender
 from .dense_slim import DenseSLIMRecommender
 from .edlae import EDLAERecommender
 from .ials import IALSRecommender
@@ -23,4 +23,4 @@ __all__ = ["BaseRecommender", "BaseSimilarityRecommender", "IALSRecommender",
            "AsymmetricCosineUserKNNRecommender", "SLIMRecommender", "DenseSLIMRecommender",
            "EDLAERecommender", "TruncatedSVDRecommender", "NMFRecommender",
            "BaseRecommenderWithEarlyStopping", "BPRFMRecommender", "TopPopRecommender",
-           "MultVAERecommender"]
+           "MultVAERecommender", "WARPFMRecommender"]

@@ -1,7 +1,8 @@
 """``BPRFMRecommender`` (irspack/recommenders/bpr.py:23-184).  The reference wraps LightFM; here the trainer is the
 library's own (``irs_bpr_*``): a synchronous mini-batch form of LightFM's per-sample step -
 BPR loss, Adagrad, item biases - whose sampling, gradients and updates run on the device and are reproducible to
-the byte.  ``loss="warp"`` is not implemented."""
+the byte.  The WARP loss (section 14, "WARP") is ``BPRFMTrainer(loss="warp")`` and ``WARPFMRecommender``;
+``BPRFMRecommender(loss="warp")`` still refuses."""
 import ctypes as C
 import pickle
 from typing import IO, Any, Dict, Optional
@@ -24,16 +25,16 @@ class BPRFMTrainer(TrainerBase):
     def __init__(self, X: Any, n_components: int, item_alpha: float, user_alpha: float, loss: str = "bpr",
                  n_threads: int = 1, learning_rate: float = 0.05, batch_size: int = 4096, random_seed: int = 42,
                  device: Optional[int] = None, user_init: Optional[np.ndarray] = None,
-                 item_init: Optional[np.ndarray] = None) -> None:
-        if loss == "warp":
-            raise NotImplementedError('BPRFM loss "warp" is not implemented on the device: use loss="bpr".')
-        if loss != "bpr":
+                 item_init: Optional[np.ndarray] = None, max_sampled: int = 10) -> None:
+        if loss not in ("bpr", "warp"):
             raise ValueError('BPRFM loss must be either "bpr" or "warp".')
+        self.loss = loss
         _, indptr, indices, data = _lib.csr_arrays(X, np.float32)
         self.n_users, self.n_items = int(X.shape[0]), int(X.shape[1])
         self.hyper: Dict[str, Any] = dict(
             n_components=int(n_components), item_alpha=float(item_alpha), user_alpha=float(user_alpha),
-            learning_rate=float(learning_rate), batch_size=int(batch_size), random_seed=int(random_seed))
+            learning_rate=float(learning_rate), batch_size=int(batch_size), random_seed=int(random_seed),
+            loss=loss, max_sampled=int(max_sampled) if loss == "warp" else 0)
         self.n_threads = n_threads
         self.device = _lib.default_device() if device is None else int(device)
         self._h = C.c_void_p()
@@ -45,11 +46,14 @@ class BPRFMTrainer(TrainerBase):
                 if table.shape != (rows, int(n_components)):
                     raise ValueError(f"an initial table has shape {table.shape}, expected {(rows, int(n_components))}.")
             inits.append(table)
-        check(lib().irs_bpr_create(
-            self.n_users, self.n_items, ptr(indptr, C.c_int64), ptr(indices, C.c_int32), ptr(data, C.c_float),
-            int(n_components), float(user_alpha), float(item_alpha), float(learning_rate), int(batch_size),
-            C.c_uint64(int(random_seed) & (2 ** 64 - 1)), *(None if t is None else ptr(t, C.c_float) for t in inits),
-            self.device, C.byref(self._h)))
+        args = [self.n_users, self.n_items, ptr(indptr, C.c_int64), ptr(indices, C.c_int32), ptr(data, C.c_float),
+                int(n_components), float(user_alpha), float(item_alpha), float(learning_rate), int(batch_size),
+                C.c_uint64(int(random_seed) & (2 ** 64 - 1)), *(None if t is None else ptr(t, C.c_float) for t in inits),
+                self.device]
+        if loss == "warp":
+            check(lib().irs_bpr_create_warp(*args, int(max_sampled), C.byref(self._h)))
+        else:
+            check(lib().irs_bpr_create(*args, C.byref(self._h)))
 
     def close(self) -> None:
         h, self._h = getattr(self, "_h", None), C.c_void_p()
@@ -85,6 +89,45 @@ class BPRFMTrainer(TrainerBase):
             raise ValueError("users, pos and neg must have one length.")
         self.version += 1
         check(lib().irs_bpr_step_triples(self._h, arrays[0].size, *(ptr(a, C.c_int32) for a in arrays)))
+
+    # ---- loss="warp" ----------------------------------------------------------------------------------------
+    def candidates(self, epoch: int, first: int = 0, count: Optional[int] = None):
+        """``(users, positives, cand)`` of ``epoch`` at positions ``[first, first + count)``; ``cand`` is
+        ``count x max_sampled``, candidate ``t`` of a position in column ``t - 1``"""
+        if count is None:
+            count = self.epoch_length - int(first)
+        n = max(int(count), 0)
+        users, pos = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        cand = np.zeros((n, self.hyper["max_sampled"]), dtype=np.int32)
+        check(lib().irs_bpr_warp_candidates(self._h, int(epoch), int(first), int(count),
+                                            *(ptr(a, C.c_int32) for a in (users, pos, cand))))
+        return users, pos, cand
+
+    def _warp_batch(self, users: Any, pos: Any, cand: Any):
+        users, pos = (np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (users, pos))
+        cand = np.ascontiguousarray(cand, dtype=np.int32)
+        if users.size != pos.size or cand.shape != (users.size, self.hyper["max_sampled"]):
+            raise ValueError("users and pos must have one length n, and cand the shape (n, max_sampled).")
+        return users, pos, cand
+
+    def search(self, users: Any, pos: Any, cand: Any):
+        """the WARP search on the current state, nothing updated: ``(neg, tries)`` - per position the first
+        candidate that violates the margin (-1: none) and the number of candidates examined"""
+        users, pos, cand = self._warp_batch(users, pos, cand)
+        neg, tries = np.zeros(users.size, dtype=np.int32), np.zeros(users.size, dtype=np.int32)
+        check(lib().irs_bpr_warp_search(self._h, users.size, *(ptr(a, C.c_int32) for a in (users, pos, cand, neg, tries))))
+        return neg, tries
+
+    def step_candidates(self, users: Any, pos: Any, cand: Any) -> None:
+        """one synchronous WARP batch on the caller's positions and candidates"""
+        users, pos, cand = self._warp_batch(users, pos, cand)
+        self.version += 1
+        check(lib().irs_bpr_warp_step(self._h, users.size, *(ptr(a, C.c_int32) for a in (users, pos, cand))))
+
+    def warp_stats(self) -> Dict[str, Any]:
+        st = _lib.BprWarpStatsStruct()
+        check(lib().irs_bpr_warp_stats(self._h, C.byref(st)))
+        return {name: getattr(st, name) for name, _ in _lib.BprWarpStatsStruct._fields_ if name != "reserved"}
 
     def get_state(self) -> Dict[str, Any]:
         k = self.hyper["n_components"]
@@ -123,8 +166,10 @@ class BPRFMTrainer(TrainerBase):
 
     def load_state(self, ifs: IO) -> None:
         state = pickle.load(ifs)
-        if state.get("hyper", self.hyper) != self.hyper:
-            raise ValueError(f"the saved state was trained with {state['hyper']}, this trainer has {self.hyper}.")
+        saved = state.get("hyper", self.hyper)
+        # (a state saved before the trainer knew a loss is a BPR state)
+        if dict(dict(loss="bpr", max_sampled=0), **saved) != self.hyper:
+            raise ValueError(f"the saved state was trained with {saved}, this trainer has {self.hyper}.")
         self.set_state(state)
 
 
@@ -208,3 +253,23 @@ class BPRFMRecommender(BaseRecommenderWithEarlyStopping):
             items = np.ascontiguousarray(np.concatenate([t["V"], t["b"][:, None]], axis=1).T)
             held = t["_augmented"] = (users, items)
         return held
+
+
+class WARPFMRecommender(BPRFMRecommender):
+    """The reference's ``BPRFMRecommender(loss="warp")`` (bpr.py:100-105) as a class of its own: the WARP ranking loss
+    in the library's synchronous form ("WARP"), with ``max_sampled`` - for which the reference's
+    constructor has no place - as a keyword.  Scoring, early stopping and the ``K + 1`` factor form are the parent's."""
+
+    def __init__(self, X_train_all: Any, n_components: int = 128, item_alpha: float = 1e-9, user_alpha: float = 1e-9,
+                 n_threads: Optional[int] = None, train_epochs: int = 128, *, max_sampled: int = 10,
+                 learning_rate: float = 0.05, batch_size: int = 4096, random_seed: int = 42,
+                 device: Optional[int] = None) -> None:
+        super().__init__(X_train_all, n_components, item_alpha, user_alpha, "bpr", n_threads, train_epochs,
+                         learning_rate=learning_rate, batch_size=batch_size, random_seed=random_seed, device=device)
+        self.loss = "warp"
+        self.max_sampled = max_sampled
+
+    def _create_trainer(self) -> BPRFMTrainer:
+        return BPRFMTrainer(self.X_train_all, self.n_components, self.item_alpha, self.user_alpha, "warp",
+                            self.n_threads, learning_rate=self.learning_rate, batch_size=self.batch_size,
+                            random_seed=self.random_seed, device=self.device, max_sampled=self.max_sampled)
