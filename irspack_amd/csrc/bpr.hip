@@ -14,7 +14,8 @@
 
 #include "bpr_kernels.hpp"
 #include "common.hpp"
-#include "gram_setup.hpp"
+#include "csr_checks.hpp"
+#include "phase_spans.hpp"
 
 namespace irs {
 namespace bpr {
@@ -33,14 +34,13 @@ struct irs_bpr {
   uint64_t seed = 0;
   unsigned long long batch_no = 0;  // of this handle, never reused: the stamps compare against it
   irs::bpr::Positives positives;
-  bool on_device = false, timed = false;
+  bool on_device = false;
   std::vector<float> h_tables[6];  // U, V, b, GU, GV, Gb (unpadded) until the first device call
   irs::DeviceBuffer<float> U, V, b, GU, GV, Gb;
   irs::DeviceBuffer<unsigned long long> accU, accV, accb, stampU, stampV;
   irs::DeviceBuffer<int32_t> indptr, indices, pos_user, pos_item, t_user, t_pos, t_neg, diverged;
-  std::vector<std::unique_ptr<irs::slim::Event>> ev;
-  std::vector<int> ev_phase;
-  double ms[irs::bpr::PH_COUNT] = {0, 0, 0}, epoch_ms = 0;
+  irs::PhaseSpans<irs::bpr::PH_COUNT> spans;  // on with IRSPACK_AMD_BPR_PHASES
+  double epoch_ms = 0;
   // loss "warp" (max_sampled >= 1; 0 is a BPR handle): the weight table, the caller's candidates, the tries of the
   // search probe and the counters of the search kernel
   int32_t max_sampled = 0, in_flight = 0;
@@ -53,25 +53,6 @@ struct irs_bpr {
 
 namespace irs {
 namespace bpr {
-
-struct Span {
-  irs_bpr &t;
-  hipStream_t s;
-  Span(irs_bpr &t_, int phase, hipStream_t s_) : t(t_), s(s_) { mark(phase); }
-  void stop() { mark(-1); }
-  void mark(int phase) {
-    if (!t.timed) return;
-    t.ev.emplace_back(new slim::Event());
-    t.ev_phase.push_back(phase);
-    IRS_HIP(hipEventRecord(t.ev.back()->e, s));
-  }
-};
-
-static void fold_events(irs_bpr &t) {
-  for (size_t i = 0; i + 1 < t.ev.size(); i += 2) t.ms[t.ev_phase[i]] += slim::elapsed_ms(*t.ev[i], *t.ev[i + 1]);
-  t.ev.clear();
-  t.ev_phase.clear();
-}
 
 // a (rows x k) host table <-> its (rows x kp) device image; the padding holds `pad`
 static void upload_table(DeviceBuffer<float> &d, const float *h, int64_t rows, int32_t k, int32_t kp, float pad,
@@ -155,7 +136,7 @@ static void step(irs_bpr &t, int64_t n, hipStream_t s) {
   const double scale = std::ldexp(1.0, scale_log2(n));
   t.batch_no++;
   {
-    Span sp(t, PH_GRAD, s);
+    auto sp = t.spans.span(PH_GRAD, s);
     switch (t.lanes) {
       case 1: launch_grad<1, 1>(t, n, scale, s); break;
       case 2: launch_grad<2, 1>(t, n, scale, s); break;
@@ -170,7 +151,7 @@ static void step(irs_bpr &t, int64_t n, hipStream_t s) {
     IRS_HIP(hipGetLastError());
     sp.stop();
   }
-  Span sp(t, PH_APPLY, s);
+  auto sp = t.spans.span(PH_APPLY, s);
   switch (t.lanes) {
     case 1: launch_apply<1>(t, n, scale, s); break;
     case 2: launch_apply<2>(t, n, scale, s); break;
@@ -238,11 +219,11 @@ template <bool GEN> static void warp_step(irs_bpr &t, int64_t n, int64_t epoch, 
   const double scale = std::ldexp(1.0, warp_scale_log2(n));
   t.batch_no++;
   {
-    Span sp(t, PH_GRAD, s);
+    auto sp = t.spans.span(PH_GRAD, s);
     launch_search_lanes<GEN, true>(t, n, epoch, first, scale, s);
     sp.stop();
   }
-  Span sp(t, PH_APPLY, s);
+  auto sp = t.spans.span(PH_APPLY, s);
   switch (t.lanes) {
     case 1: launch_warp_apply<1>(t, n, scale, s); break;
     case 2: launch_warp_apply<2>(t, n, scale, s); break;
@@ -317,7 +298,7 @@ static void create(int64_t n_users, int64_t n_items, const int64_t *indptr, cons
                    uint64_t seed, const float *user_init, const float *item_init, int32_t device, int32_t max_sampled,
                    irs_bpr **out) {
   check_arg(out != nullptr, "out must not be null.");
-  bpr::validate_matrix(n_users, n_items, indptr, indices, data);
+  validate_finite_matrix(n_users, n_items, indptr, indices, data);
   bpr::validate_hyper(k, user_alpha, item_alpha, learning_rate, batch_size);
   if (user_init)
     bpr::validate_table(user_init, n_users * k, "the initial user table holds a non-finite value.",
@@ -331,7 +312,7 @@ static void create(int64_t n_users, int64_t n_items, const int64_t *indptr, cons
   t->lanes = bpr::lanes_per_triple(k);
   t->user_alpha = user_alpha, t->item_alpha = item_alpha, t->lr = learning_rate, t->batch_size = batch_size;
   t->seed = seed;
-  t->timed = env_flag("IRSPACK_AMD_BPR_PHASES", false);
+  t->spans.enabled = env_flag("IRSPACK_AMD_BPR_PHASES", false);
   t->positives = bpr::filter_positives(n_users, n_items, indptr, indices, data);
   t->n_used = static_cast<int64_t>(t->positives.pos_user.size());
   const size_t nu = static_cast<size_t>(n_users) * k, ni = static_cast<size_t>(n_items) * k;
@@ -387,13 +368,13 @@ irs_status irs_bpr_run_epochs(irs_bpr *t, int64_t n_epochs) {
     hipStream_t s = nullptr;
     for (int64_t e = 0; e < n_epochs; e++) {
       const bool last = e + 1 == n_epochs;
-      slim::Event e0, e1;
+      Event e0, e1;
       if (last) {
-        std::fill(t->ms, t->ms + bpr::PH_COUNT, 0.0);
+        std::fill(t->spans.ms, t->spans.ms + bpr::PH_COUNT, 0.0);
         IRS_HIP(hipEventRecord(e0.e, s));
       }
-      const bool timed = t->timed;
-      t->timed = timed && last;
+      const bool timed = t->spans.enabled;
+      t->spans.enabled = timed && last;
       const bool warp = t->max_sampled > 0;
       if (warp && last) t->counters.zero(s);
       for (int64_t first = 0; first < t->n_used; first += t->batch_size) {
@@ -402,18 +383,18 @@ irs_status irs_bpr_run_epochs(irs_bpr *t, int64_t n_epochs) {
           bpr::warp_step<true>(*t, n, t->epoch, first, s);
           continue;
         }
-        bpr::Span sp(*t, bpr::PH_SAMPLE, s);
+        auto sp = t->spans.span(bpr::PH_SAMPLE, s);
         bpr::launch_sample(*t, t->epoch, first, n, s);
         sp.stop();
         bpr::step(*t, n, s);
       }
-      t->timed = timed;
+      t->spans.enabled = timed;
       t->epoch++;
       if (last) {
         IRS_HIP(hipEventRecord(e1.e, s));
         IRS_HIP(hipStreamSynchronize(s));
-        t->epoch_ms = slim::elapsed_ms(e0, e1);
-        bpr::fold_events(*t);
+        t->epoch_ms = elapsed_ms(e0, e1);
+        t->spans.fold();
         if (warp) {
           bpr::read_counters(*t, t->epoch_counts);
           std::copy(t->epoch_counts, t->epoch_counts + 3, t->call_counts);
@@ -436,8 +417,8 @@ irs_status irs_bpr_sample(irs_bpr *t, int64_t epoch, int64_t first, int64_t coun
     check_arg(count == 0 || (users && pos && neg), "the triple arrays must not be null.");
     bpr::to_device(*t);
     hipStream_t s = nullptr;
-    const bool timed = t->timed;
-    t->timed = false;
+    const bool timed = t->spans.enabled;
+    t->spans.enabled = false;
     const int64_t cap = static_cast<int64_t>(t->t_user.count);
     for (int64_t done = 0; done < count; done += cap) {
       const int64_t n = std::min(cap, count - done);
@@ -448,7 +429,7 @@ irs_status irs_bpr_sample(irs_bpr *t, int64_t epoch, int64_t first, int64_t coun
       IRS_HIP(hipMemcpyAsync(neg + done, t->t_neg.ptr, bytes, hipMemcpyDeviceToHost, s));
     }
     IRS_HIP(hipStreamSynchronize(s));
-    t->timed = timed;
+    t->spans.enabled = timed;
   });
 }
 
@@ -465,10 +446,10 @@ irs_status irs_bpr_step_triples(irs_bpr *t, int64_t n, const int32_t *users, con
     IRS_HIP(hipMemcpyAsync(t->t_user.ptr, users, cnt * sizeof(int32_t), hipMemcpyHostToDevice, s));
     IRS_HIP(hipMemcpyAsync(t->t_pos.ptr, pos, cnt * sizeof(int32_t), hipMemcpyHostToDevice, s));
     IRS_HIP(hipMemcpyAsync(t->t_neg.ptr, neg, cnt * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    const bool timed = t->timed;
-    t->timed = false;
+    const bool timed = t->spans.enabled;
+    t->spans.enabled = false;
     bpr::step(*t, n, s);
-    t->timed = timed;
+    t->spans.enabled = timed;
     IRS_HIP(hipStreamSynchronize(s));
     bpr::check_diverged(*t);
   });
@@ -531,9 +512,9 @@ irs_status irs_bpr_stats(irs_bpr *t, irs_bpr_stats_t *out) {
     out->lanes_per_triple = t->lanes;
     out->scale_log2 = bpr::scale_log2(std::max<int64_t>(1, std::min(t->batch_size, t->n_used)));
     out->epoch_ms = t->epoch_ms;
-    out->sample_ms = t->ms[bpr::PH_SAMPLE];
-    out->grad_ms = t->ms[bpr::PH_GRAD];
-    out->apply_ms = t->ms[bpr::PH_APPLY];
+    out->sample_ms = t->spans.ms[bpr::PH_SAMPLE];
+    out->grad_ms = t->spans.ms[bpr::PH_GRAD];
+    out->apply_ms = t->spans.ms[bpr::PH_APPLY];
   });
 }
 
@@ -591,10 +572,10 @@ irs_status irs_bpr_warp_step(irs_bpr *t, int64_t n, const int32_t *users, const 
     bpr::to_device(*t);
     hipStream_t s = nullptr;
     bpr::upload_warp_batch(*t, n, users, pos, cand, s);
-    const bool timed = t->timed;
-    t->timed = false;
+    const bool timed = t->spans.enabled;
+    t->spans.enabled = false;
     bpr::warp_step<false>(*t, n, 0, 0, s);
-    t->timed = timed;
+    t->spans.enabled = timed;
     IRS_HIP(hipStreamSynchronize(s));
     bpr::read_counters(*t, t->call_counts);
     bpr::check_diverged(*t);
@@ -614,8 +595,8 @@ irs_status irs_bpr_warp_stats(irs_bpr *t, irs_bpr_warp_stats_t *out) {
     out->call_positions = t->call_counts[0], out->call_updates = t->call_counts[1];
     out->call_tries = t->call_counts[2];
     out->epoch_ms = t->epoch_ms;
-    out->search_ms = t->ms[bpr::PH_GRAD];
-    out->apply_ms = t->ms[bpr::PH_APPLY];
+    out->search_ms = t->spans.ms[bpr::PH_GRAD];
+    out->apply_ms = t->spans.ms[bpr::PH_APPLY];
   });
 }
 

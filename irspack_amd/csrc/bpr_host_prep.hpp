@@ -103,31 +103,7 @@ inline float init_value(uint64_t seed, uint64_t table, uint64_t index, int32_t k
 }
 
 // ---- argument checks -------------------------------------------------------------------------------------------
-// the matrix checks of irs_truncsvd_create: gram_setup.hpp's validate_csr (restated here without HIP) and every
-// value finite
-inline int64_t validate_matrix(int64_t rows, int64_t cols, const int64_t *indptr, const int32_t *indices,
-                               const float *data) {
-  check_arg(rows >= 0 && cols >= 0 && indptr && indptr[0] == 0, "bad matrix.");
-  check_arg(rows < (int64_t(1) << 31) - 1 && cols < (int64_t(1) << 31) - 1, "rows and cols must be below 2^31.");
-  for (int64_t i = 0; i < rows; i++) check_arg(indptr[i + 1] >= indptr[i], "malformed indptr.");
-  const int64_t nnz = indptr[rows];
-  check_arg(nnz < (int64_t(1) << 31), "nnz must be below 2^31.");
-  check_arg(nnz == 0 || (indices && data), "bad matrix.");
-  for (int64_t i = 0; i < rows; i++) {
-    int64_t prev = -1;
-    for (int64_t q = indptr[i]; q < indptr[i + 1]; q++) {
-      const int64_t c = indices[q];
-      check_arg(c >= 0 && c < cols, "column index out of range.");
-      check_arg(c != prev, "duplicate column index in a row (sum duplicates before the call).");
-      check_arg(c > prev, "column indices of a row must be sorted.");
-      prev = c;
-    }
-  }
-  check_arg(rows >= 1 && cols >= 1, "the matrix must have at least one row and one column.");
-  for (int64_t q = 0; q < nnz; q++) check_arg(std::isfinite(data[q]), "the matrix holds a non-finite value.");
-  return nnz;
-}
-
+// (the matrix itself: csr_checks.hpp's validate_finite_matrix)
 inline void validate_hyper(int32_t k, float user_alpha, float item_alpha, float learning_rate, int64_t batch_size) {
   check_arg(k >= 1, "k must be >= 1.");
   check_arg(k <= MAX_K, "k must be <= 512.");

@@ -19,10 +19,11 @@
 // through ridge_mfma_64.  No float atomics; every sum has a fixed order: two calls give identical bytes.
 #include <cmath>
 
-#include "chol_tile_kernels.hpp"
 #include "common.hpp"
+#include "csr_checks.hpp"
 #include "gram_setup.hpp"
-#include "tri_inv_kernels.hpp"
+#include "phase_spans.hpp"
+#include "tile_solver_calls.hpp"
 
 namespace irs {
 namespace dslim {
@@ -131,7 +132,7 @@ static void fit(int64_t rows, int64_t cols, const int64_t *indptr, const int32_t
                              std::to_string(static_cast<int64_t>(need / 1048576.0)) + " MiB of device memory, " +
                              std::to_string(free_b >> 20) + " MiB are free.");
 
-  slim::Event e0, e1, e2, e3, e4, e5;
+  Event e0, e1, e2, e3, e4, e5;
   IRS_HIP(hipEventRecord(e0.e, s));
   DeviceBuffer<float> d_A, d_Wk;
   DeviceBuffer<int32_t> d_flag;
@@ -148,16 +149,7 @@ static void fit(int64_t rows, int64_t cols, const int64_t *indptr, const int32_t
 
   // P = L L^T
   float *A = d_A.ptr;
-  for (int64_t k = 0; k < nb; k++) {
-    hipLaunchKernelGGL(ials::ridge_chol_diag_kernel, dim3(1), dim3(256), 0, s, A, np, static_cast<int>(k),
-                       d_flag.ptr);
-    const int64_t below = n_pad - (k + 1) * RIDGE_NB, m = nb - k - 1;
-    if (below <= 0) continue;
-    hipLaunchKernelGGL(ials::ridge_chol_trsm_kernel, dim3(static_cast<unsigned>(ceil_div(below, 256))), dim3(256), 0,
-                       s, A, np, static_cast<int>(k));
-    hipLaunchKernelGGL(ials::ridge_chol_update_kernel, dim3(static_cast<unsigned>(m * (m + 1) / 2)), dim3(256), 0, s,
-                       A, np, static_cast<int>(k));
-  }
+  launch_tile_cholesky(A, np, nb, d_flag.ptr, s);
   IRS_HIP(hipGetLastError());
   IRS_HIP(hipEventRecord(e2.e, s));
   int32_t flag = 0;
@@ -178,17 +170,7 @@ static void fit(int64_t rows, int64_t cols, const int64_t *indptr, const int32_t
   d_Wk.alloc(NP2);
   d_Wk.zero(s);
   float *M = d_Wk.ptr;
-  hipLaunchKernelGGL(dslim_diag_inv_kernel, dim3(static_cast<unsigned>(nb)), dim3(64), 0, s,
-                     static_cast<const float *>(A), np, M);
-  for (int64_t k = 0; k < nb; k++) {
-    if (k > 0)
-      hipLaunchKernelGGL(dslim_inv_row_kernel, dim3(static_cast<unsigned>(k)), dim3(256), 0, s, M, np,
-                         static_cast<int>(k));
-    if (k + 1 < nb)
-      hipLaunchKernelGGL(dslim_inv_update_kernel,
-                         dim3(static_cast<unsigned>(nb - k - 1), static_cast<unsigned>(k + 1)), dim3(256), 0, s,
-                         static_cast<const float *>(A), M, np, static_cast<int>(k));
-  }
+  launch_tile_tri_inverse(A, M, np, nb, s);
   hipLaunchKernelGGL(dslim_mtm_kernel, dim3(static_cast<unsigned>(nb * (nb + 1) / 2)), dim3(256), 0, s,
                      static_cast<const float *>(M), np, A);
   IRS_HIP(hipGetLastError());
@@ -204,11 +186,11 @@ static void fit(int64_t rows, int64_t cols, const int64_t *indptr, const int32_t
   IRS_HIP(hipEventRecord(e5.e, s));
   IRS_HIP(hipStreamSynchronize(s));
   if (stats) {
-    stats->gram_ms = slim::elapsed_ms(e0, e1);
-    stats->factor_ms = slim::elapsed_ms(e1, e2);
-    stats->invert_ms = slim::elapsed_ms(e2, e3);
-    stats->finalize_ms = slim::elapsed_ms(e3, e4);
-    stats->d2h_ms = slim::elapsed_ms(e4, e5);
+    stats->gram_ms = elapsed_ms(e0, e1);
+    stats->factor_ms = elapsed_ms(e1, e2);
+    stats->invert_ms = elapsed_ms(e2, e3);
+    stats->finalize_ms = elapsed_ms(e3, e4);
+    stats->d2h_ms = elapsed_ms(e4, e5);
   }
 }
 
@@ -223,7 +205,7 @@ irs_status irs_dense_slim_fit(int64_t rows, int64_t cols, const int64_t *indptr,
                               const float *data, float reg, float diag_scale, int32_t device, float *W,
                               irs_dense_slim_stats *stats) {
   return guard([&] {
-    slim::validate_csr(rows, cols, indptr, indices, data);
+    validate_csr(rows, cols, indptr, indices, data);
     check_arg(cols == 0 || W != nullptr, "W must not be null.");
     dslim::fit(rows, cols, indptr, indices, data, reg, diag_scale, device, W, stats);
   });

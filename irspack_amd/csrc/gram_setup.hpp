@@ -1,6 +1,6 @@
 // The dense item Gram matrix G = X^T X on the device, shared by SLIM (slim.hip) and EASE / EDLAE
-// (dense_slim.hip): the validation of the caller's CSR arrays, the upload of X by rows and by columns,
-// the longest-first order and gram_rows_kernel itself.
+// (dense_slim.hip): the upload of X by rows and by columns, the longest-first order and gram_rows_kernel
+// itself.
 #pragma once
 #include <algorithm>
 #include <numeric>
@@ -41,46 +41,6 @@ static __global__ __launch_bounds__(256) void gram_rows_kernel(const int32_t *__
       row[g] += xv * rval[q];
     }
   }
-}
-
-struct Event {
-  hipEvent_t e = nullptr;
-  Event() { IRS_HIP(hipEventCreate(&e)); }
-  ~Event() {
-    if (e) (void)hipEventDestroy(e);
-  }
-  Event(const Event &) = delete;
-  Event &operator=(const Event &) = delete;
-};
-
-inline double elapsed_ms(const Event &a, const Event &b) {
-  float ms = 0.f;
-  IRS_HIP(hipEventElapsedTime(&ms, a.e, b.e));
-  return static_cast<double>(ms);
-}
-
-// Invalid-argument checks of a CSR matrix handed to the C ABI, before any device work: monotone indptr,
-// sizes below 2^31, indices in range and strictly ascending within a row (the Gram kernel's lanes must
-// hit distinct elements).  Returns nnz.
-inline int64_t validate_csr(int64_t rows, int64_t cols, const int64_t *indptr, const int32_t *indices,
-                            const float *data) {
-  check_arg(rows >= 0 && cols >= 0 && indptr && indptr[0] == 0, "bad matrix.");
-  check_arg(rows < (int64_t(1) << 31) - 1 && cols < (int64_t(1) << 31) - 1, "rows and cols must be below 2^31.");
-  for (int64_t i = 0; i < rows; i++) check_arg(indptr[i + 1] >= indptr[i], "malformed indptr.");
-  const int64_t nnz = indptr[rows];
-  check_arg(nnz < (int64_t(1) << 31), "nnz must be below 2^31.");
-  check_arg(nnz == 0 || (indices && data), "bad matrix.");
-  for (int64_t i = 0; i < rows; i++) {
-    int64_t prev = -1;
-    for (int64_t q = indptr[i]; q < indptr[i + 1]; q++) {
-      const int64_t c = indices[q];
-      check_arg(c >= 0 && c < cols, "column index out of range.");
-      check_arg(c != prev, "duplicate column index in a row (sum duplicates before the call).");
-      check_arg(c > prev, "column indices of a row must be sorted.");
-      prev = c;
-    }
-  }
-  return nnz;
 }
 
 // X by rows and by columns on the device and the order in which the rows of G are handed out

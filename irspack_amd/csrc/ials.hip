@@ -28,6 +28,7 @@
 #include "ials_pp_kernels.hpp"
 #include "ials_feature_kernels.hpp"
 #include "ials_ridge_kernels.hpp"
+#include "tile_solver_calls.hpp"
 #include "ials_short_kernels.hpp"
 #include "ials_gk_kernels.hpp"
 #include "ials_eig_kernels.hpp"
@@ -2120,17 +2121,7 @@ void launch_ridge_factorize(irs_ials_trainer *t, int which) {
                        static_cast<int>(n_tiles), static_cast<int>(n_slabs), static_cast<int>(F),
                        static_cast<int>(FP), lam, t->f_L[which].ptr);
   }
-  float *L = t->f_L[which].ptr;
-  for (int64_t k = 0; k < nb; k++) {
-    hipLaunchKernelGGL(ridge_chol_diag_kernel, dim3(1), dim3(256), 0, s, L, static_cast<int>(FP),
-                       static_cast<int>(k), t->err_flag.ptr);
-    const int64_t below = FP - (k + 1) * RIDGE_NB, m = nb - k - 1;
-    if (below <= 0) continue;
-    hipLaunchKernelGGL(ridge_chol_trsm_kernel, dim3(ceil_div(below, 256)), dim3(256), 0, s, L,
-                       static_cast<int>(FP), static_cast<int>(k));
-    hipLaunchKernelGGL(ridge_chol_update_kernel, dim3(m * (m + 1) / 2), dim3(256), 0, s, L,
-                       static_cast<int>(FP), static_cast<int>(k));
-  }
+  launch_tile_cholesky(t->f_L[which].ptr, static_cast<int>(FP), nb, t->err_flag.ptr, s);
   t->prof.end(s);
   IRS_HIP(hipGetLastError());
 }

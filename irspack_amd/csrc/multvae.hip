@@ -12,8 +12,9 @@
 #include <cstring>
 
 #include "common.hpp"
-#include "gram_setup.hpp"
+#include "csr_checks.hpp"
 #include "multvae_kernels.hpp"
+#include "phase_spans.hpp"
 
 namespace irs {
 namespace mv {
@@ -30,7 +31,7 @@ struct irs_multvae {
   double kl_goal = 0.0;
   uint64_t seed = 0;
   irs::mv::Layout y;
-  bool on_device = false, timed = false;
+  bool on_device = false;
   std::vector<int32_t> h_indptr;                        // (kept: the offsets of a batch's dropout bytes)
   std::vector<int32_t> h_indices;                       // until the first device call
   std::vector<float> h_data;
@@ -46,32 +47,12 @@ struct irs_multvae {
   irs::DeviceBuffer<float> c_data;
   int64_t cap = 0;  // batch rows the work buffers hold
   double klc_last = 0, nll_last = 0, kl_last = 0;
-  std::vector<std::unique_ptr<irs::slim::Event>> ev;
-  std::vector<int> ev_phase;
-  double ms[irs::mv::PH_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0}, epoch_ms = 0;
+  irs::PhaseSpans<irs::mv::PH_COUNT> spans;  // on with IRSPACK_AMD_MULTVAE_PHASES
+  double epoch_ms = 0;
 };
 
 namespace irs {
 namespace mv {
-
-struct Span {
-  irs_multvae &t;
-  hipStream_t s;
-  Span(irs_multvae &t_, int phase, hipStream_t s_) : t(t_), s(s_) { mark(phase); }
-  void stop() { mark(-1); }
-  void mark(int phase) {
-    if (!t.timed) return;
-    t.ev.emplace_back(new slim::Event());
-    t.ev_phase.push_back(phase);
-    IRS_HIP(hipEventRecord(t.ev.back()->e, s));
-  }
-};
-
-static void fold_events(irs_multvae &t) {
-  for (size_t i = 0; i + 1 < t.ev.size(); i += 2) t.ms[t.ev_phase[i]] += slim::elapsed_ms(*t.ev[i], *t.ev[i + 1]);
-  t.ev.clear();
-  t.ev_phase.clear();
-}
 
 // the host tables of one group (0: parameters, 1: m, 2: v) <-> an arena on the device
 static void upload_arena(irs_multvae &t, int group, DeviceBuffer<float> &d, hipStream_t s) {
@@ -211,12 +192,12 @@ static void forward(irs_multvae &t, const SparseRows &x, int64_t n, bool evaluat
   const Layout &y = t.y;
   const float *th = t.theta.ptr;
   {
-    Span sp(t, PH_ENCODE, s);
+    auto sp = t.spans.span(PH_ENCODE, s);
     launch_encode_input(t, x, n, evaluate ? 1.f : 1.f / (1.f - t.dropout_p), s);
     sp.stop();
   }
   {
-    Span sp(t, PH_DENSE, s);
+    auto sp = t.spans.span(PH_DENSE, s);
     forward_dense<EPI_NONE>(n, 2 * y.L, y.H + 1, t.h1a.ptr, y.H + 1, th + y.seg[1], 2 * y.L, t.ml.ptr, 2 * y.L, s);
     hipLaunchKernelGGL(mv_latent_forward_kernel, dim3(static_cast<unsigned>(n)), dim3(BLOCK), 0, s,
                        static_cast<int32_t>(y.L), static_cast<int32_t>(y.Hd), x.rows, static_cast<const float *>(t.ml.ptr),
@@ -225,7 +206,7 @@ static void forward(irs_multvae &t, const SparseRows &x, int64_t n, bool evaluat
     forward_dense<EPI_TANH>(n, y.Hd, y.L + 1, t.za.ptr, y.L + 1, th + y.seg[2], y.Hd, t.h2a.ptr, y.Hd + 1, s);
     sp.stop();
   }
-  Span sp(t, PH_LOGIT, s);
+  auto sp = t.spans.span(PH_LOGIT, s);
   gemm<false, false, EPI_NONE>(n, y.I, y.Hd + 1, t.h2a.ptr, y.Hd + 1, th + y.seg[3], y.I, t.block.ptr, y.I, nullptr, 0, s);
   sp.stop();
 }
@@ -246,22 +227,22 @@ static void step(irs_multvae &t, int64_t n, double klc, bool own_keep, bool own_
   float *th = t.theta.ptr, *G = t.G_arena.ptr;
   forward(t, x, n, false, noise_key(t.seed, t.n_updates, 1), own_eps ? t.eps.ptr : nullptr, s);
   {
-    Span sp(t, PH_SOFTMAX, s);
+    auto sp = t.spans.span(PH_SOFTMAX, s);
     launch_softmax(t, x, n, SM_GRADIENT, s);
     sp.stop();
   }
   {
-    Span sp(t, PH_DW4, s);
+    auto sp = t.spans.span(PH_DW4, s);
     gemm_slabs<true, false, EPI_NONE>(t, y.Hd + 1, y.I, n, DW4_SLAB, t.h2a.ptr, y.Hd + 1, t.block.ptr, y.I, G + y.seg[3], y.I, nullptr, 0, s);
     sp.stop();
   }
   {
-    Span sp(t, PH_DH2, s);
+    auto sp = t.spans.span(PH_DH2, s);
     gemm_slabs<false, true, EPI_DTANH>(t, n, y.Hd, y.I, dh2_slab(y.I), t.block.ptr, y.I, th + y.seg[3], y.I, t.da3.ptr, y.Hd, t.h2a.ptr, y.Hd + 1, s);
     sp.stop();
   }
   {
-    Span sp(t, PH_DENSE, s);
+    auto sp = t.spans.span(PH_DENSE, s);
     gemm<true, false, EPI_NONE>(y.L + 1, y.Hd, n, t.za.ptr, y.L + 1, t.da3.ptr, y.Hd, G + y.seg[2], y.Hd, nullptr, 0, s);
     gemm<false, true, EPI_NONE>(n, y.L, y.Hd, t.da3.ptr, y.Hd, th + y.seg[2], y.Hd, t.dz.ptr, y.L, nullptr, 0, s);
     hipLaunchKernelGGL(mv_latent_backward_kernel, dim3(static_cast<unsigned>(ceil_div(n * y.L, BLOCK))), dim3(BLOCK), 0, s,
@@ -275,12 +256,12 @@ static void step(irs_multvae &t, int64_t n, double klc, bool own_keep, bool own_
   }
   const double scale = std::ldexp(1.0, scale_log2(n));
   {
-    Span sp(t, PH_DW1, s);
+    auto sp = t.spans.span(PH_DW1, s);
     launch_dw1(t, x, n, scale, s);
     sp.stop();
   }
   {
-    Span sp(t, PH_ADAM, s);
+    auto sp = t.spans.span(PH_ADAM, s);
     hipLaunchKernelGGL(mv_adam_kernel, dim3(static_cast<unsigned>(ceil_div(y.total, BLOCK))), dim3(BLOCK), 0, s, y.total,
                        y.w1_count, static_cast<int32_t>(y.Hp), th, t.m.ptr, t.v.ptr, G, t.acc.ptr, 1.0 / scale, t.lr,
                        static_cast<float>(bias_correction(0.9, t.n_updates)),
@@ -315,8 +296,8 @@ template <class F>
 static void for_caller_rows(irs_multvae &t, int64_t rows, const int64_t *indptr, const int32_t *indices, const float *data,
                             F &&fn) {
   hipStream_t s = nullptr;
-  const bool timed = t.timed;
-  t.timed = false;
+  const bool timed = t.spans.enabled;
+  t.spans.enabled = false;
   for (int64_t first = 0; first < rows; first += t.cap) {
     const int64_t n = std::min(t.cap, rows - first);
     const int64_t b = indptr[first], e = indptr[first + n];
@@ -332,14 +313,14 @@ static void for_caller_rows(irs_multvae &t, int64_t rows, const int64_t *indptr,
     fn(x, first, n, s);
     IRS_HIP(hipStreamSynchronize(s));  // (local is the source of an asynchronous copy; the buffers are reused)
   }
-  t.timed = timed;
+  t.spans.enabled = timed;
 }
 
 static void validate_caller_rows(const irs_multvae &t, int64_t rows, const int64_t *indptr, const int32_t *indices,
                                  const float *data) {
   check_arg(rows >= 0, "rows must be >= 0.");
   if (rows == 0) return;
-  bpr::validate_matrix(rows, t.n_items, indptr, indices, data);
+  validate_finite_matrix(rows, t.n_items, indptr, indices, data);
 }
 
 }  // namespace mv
@@ -356,7 +337,7 @@ irs_status irs_multvae_create(int64_t n_users, int64_t n_items, const int64_t *i
                               int32_t device, irs_multvae **out) {
   return guard([&] {
     check_arg(out != nullptr, "out must not be null.");
-    const int64_t nnz = bpr::validate_matrix(n_users, n_items, indptr, indices, data);
+    const int64_t nnz = validate_finite_matrix(n_users, n_items, indptr, indices, data);
     mv::validate_hyper(dim_z, enc_hidden, dec_hidden, dropout_p, l2_regularizer, kl_anneal_goal, anneal_end_epoch,
                        minibatch_size, learning_rate);
     const mv::Layout y = mv::make_layout(n_items, enc_hidden, dim_z, dec_hidden);
@@ -367,7 +348,7 @@ irs_status irs_multvae_create(int64_t n_users, int64_t n_items, const int64_t *i
     t->n_users = n_users, t->n_items = n_items, t->minibatch = minibatch_size, t->anneal_end_epoch = anneal_end_epoch;
     t->device = device, t->y = y, t->G = mv::lanes_per_entry(y.Hp), t->nch = mv::chunks_per_lane(y.Hp);
     t->dropout_p = dropout_p, t->l2 = l2_regularizer, t->kl_goal = kl_anneal_goal, t->lr = learning_rate, t->seed = seed;
-    t->timed = env_flag("IRSPACK_AMD_MULTVAE_PHASES", false);
+    t->spans.enabled = env_flag("IRSPACK_AMD_MULTVAE_PHASES", false);
     t->h_indptr.resize(static_cast<size_t>(n_users) + 1);
     for (int64_t u = 0; u <= n_users; u++) t->h_indptr[static_cast<size_t>(u)] = static_cast<int32_t>(indptr[u]);
     t->h_indices.assign(indices, indices + nnz);
@@ -390,13 +371,13 @@ irs_status irs_multvae_run_epochs(irs_multvae *t, int64_t n_epochs) {
     hipStream_t s = nullptr;
     for (int64_t e = 0; e < n_epochs; e++) {
       const bool last = e + 1 == n_epochs;
-      slim::Event e0, e1;
+      Event e0, e1;
       if (last) {
-        std::fill(t->ms, t->ms + mv::PH_COUNT, 0.0);
+        std::fill(t->spans.ms, t->spans.ms + mv::PH_COUNT, 0.0);
         IRS_HIP(hipEventRecord(e0.e, s));
       }
-      const bool timed = t->timed;
-      t->timed = timed && last;
+      const bool timed = t->spans.enabled;
+      t->spans.enabled = timed && last;
       const bpr::Perm perm = mv::epoch_perm(t->seed, t->epoch, t->n_users);
       for (int64_t first = 0; first < t->n_users; first += t->minibatch) {
         const int64_t n = std::min(t->minibatch, t->n_users - first);
@@ -406,13 +387,13 @@ irs_status irs_multvae_run_epochs(irs_multvae *t, int64_t n_epochs) {
         const double klc = mv::kl_coefficient(t->kl_goal, t->n_updates, t->anneal_end_epoch, t->n_users, t->minibatch);
         mv::step(*t, n, klc, false, false, last && first + t->minibatch >= t->n_users, s);
       }
-      t->timed = timed;
+      t->spans.enabled = timed;
       t->epoch++;
       if (last) {
         IRS_HIP(hipEventRecord(e1.e, s));
         IRS_HIP(hipStreamSynchronize(s));
-        t->epoch_ms = slim::elapsed_ms(e0, e1);
-        mv::fold_events(*t);
+        t->epoch_ms = elapsed_ms(e0, e1);
+        t->spans.fold();
       }
     }
     IRS_HIP(hipStreamSynchronize(s));
@@ -476,10 +457,10 @@ irs_status irs_multvae_step_batch(irs_multvae *t, int64_t n, const int32_t *user
     t->keep_ptr.upload(kp, s);
     if (keep) t->keep.upload(keep, static_cast<size_t>(kp[n]), s);
     if (eps) t->eps.upload(eps, static_cast<size_t>(n * t->y.L), s);
-    const bool timed = t->timed;
-    t->timed = false;
+    const bool timed = t->spans.enabled;
+    t->spans.enabled = false;
     mv::step(*t, n, klc, keep != nullptr, eps != nullptr, true, s);
-    t->timed = timed;
+    t->spans.enabled = timed;
     IRS_HIP(hipStreamSynchronize(s));
     mv::finish_update(*t);
     if (nll) *nll = t->nll_last;
@@ -586,9 +567,9 @@ irs_status irs_multvae_stats(irs_multvae *t, irs_multvae_stats_t *out) {
     out->klc_next = mv::kl_coefficient(t->kl_goal, t->n_updates, t->anneal_end_epoch, t->n_users, t->minibatch);
     out->klc_last = t->klc_last, out->nll_last = t->nll_last, out->kl_last = t->kl_last;
     out->epoch_ms = t->epoch_ms;
-    out->encode_ms = t->ms[mv::PH_ENCODE], out->dense_ms = t->ms[mv::PH_DENSE], out->logit_ms = t->ms[mv::PH_LOGIT];
-    out->softmax_ms = t->ms[mv::PH_SOFTMAX], out->dw4_ms = t->ms[mv::PH_DW4], out->dh2_ms = t->ms[mv::PH_DH2];
-    out->dw1_ms = t->ms[mv::PH_DW1], out->adam_ms = t->ms[mv::PH_ADAM];
+    out->encode_ms = t->spans.ms[mv::PH_ENCODE], out->dense_ms = t->spans.ms[mv::PH_DENSE], out->logit_ms = t->spans.ms[mv::PH_LOGIT];
+    out->softmax_ms = t->spans.ms[mv::PH_SOFTMAX], out->dw4_ms = t->spans.ms[mv::PH_DW4], out->dh2_ms = t->spans.ms[mv::PH_DH2];
+    out->dw1_ms = t->spans.ms[mv::PH_DW1], out->adam_ms = t->spans.ms[mv::PH_ADAM];
   });
 }
 

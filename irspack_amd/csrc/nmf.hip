@@ -3,7 +3,7 @@
 //
 // W (n_users x k) and H^T (n_items x k) live on the device as row-major blocks of row stride k_pad = k rounded
 // up to 64 with zero padding, X and X^T as CSR with the segment lists of the truncated SVD's product kernel
-// (truncsvd_plan.hpp); the product and the Gram reduce are that kernel family's with their sums in double
+// (sparse_block.hpp); the product and the Gram reduce are that kernel family's with their sums in double
 // (nmf_kernels.hpp).  One iteration is two half-steps
 //     XH = A Ht (SpMM);  G = Ht^T Ht (Gram), G[t, t] += l2;  sweep the rows of W against G and XH - l1
 // with (A, W, Ht) = (X, W, H^T) and then (X^T, H^T, W); the violation sums of both sweeps are reduced on the
@@ -13,15 +13,16 @@
 #include <algorithm>
 #include <cmath>
 
-#include "gram_setup.hpp"
+#include "csr_checks.hpp"
 #include "nmf_kernels.hpp"
+#include "phase_spans.hpp"
+#include "sparse_block.hpp"
 #include "truncsvd_kernels.hpp"
-#include "truncsvd_plan.hpp"
 
 namespace irs {
 namespace nmf {
 
-using tsvd::Csr;
+using sblock::Csr;
 using tsvd::RIDGE_NB;
 
 enum Phase { PH_SETUP = 0, PH_SPMM, PH_GRAM, PH_SWEEP, PH_D2H, PH_COUNT };
@@ -31,102 +32,38 @@ struct Fit {
   Csr X, Xt;
   DeviceBuffer<float> W, Ht, XH, G, gram_partial, spmm_partial;
   DeviceBuffer<double> partial, violation;
-  bool timed = false;
-  std::vector<std::unique_ptr<slim::Event>> ev;
-  std::vector<int> ev_phase;
-  double ms[PH_COUNT] = {0, 0, 0, 0, 0};
+  PhaseSpans<PH_COUNT> spans;  // recording only when the caller asked for the times
 };
-
-// an event pair round a phase, only when the caller asked for the times
-struct Span {
-  Fit &f;
-  hipStream_t s;
-  Span(Fit &f_, int phase, hipStream_t s_) : f(f_), s(s_) {
-    if (!f.timed) return;
-    f.ev.emplace_back(new slim::Event());
-    f.ev_phase.push_back(phase);
-    IRS_HIP(hipEventRecord(f.ev.back()->e, s));
-  }
-  void stop() {
-    if (!f.timed) return;
-    f.ev.emplace_back(new slim::Event());
-    f.ev_phase.push_back(-1);
-    IRS_HIP(hipEventRecord(f.ev.back()->e, s));
-  }
-};
-
-// (after a synchronisation)
-static void fold_events(Fit &f) {
-  for (size_t i = 0; i + 1 < f.ev.size(); i += 2) f.ms[f.ev_phase[i]] += slim::elapsed_ms(*f.ev[i], *f.ev[i + 1]);
-  f.ev.clear();
-  f.ev_phase.clear();
-}
 
 // X and X^T on the device with their segment lists (synchronises: the transpose's column counts)
 static void upload_matrix(Fit &f, const int64_t *indptr, const int32_t *indices, const float *data, hipStream_t s) {
-  Csr &X = f.X, &Xt = f.Xt;
-  X.rows = f.n_users, X.cols = f.n_items, Xt.rows = f.n_items, Xt.cols = f.n_users;
   std::vector<int32_t> h_ptr(static_cast<size_t>(f.n_users) + 1);
   for (int64_t i = 0; i <= f.n_users; i++) h_ptr[i] = static_cast<int32_t>(indptr[i]);
-  DeviceBuffer<int32_t> d_ptr;
-  d_ptr.upload(h_ptr, s);
-  X.idx.upload(indices, static_cast<size_t>(f.nnz), s);
-  X.val.upload(data, static_cast<size_t>(f.nnz), s);
-  Xt.idx.alloc(static_cast<size_t>(f.nnz));
-  Xt.val.alloc(static_cast<size_t>(f.nnz));
-  std::vector<int32_t> col_count(static_cast<size_t>(f.n_items), 0);
-  DeviceBuffer<char> tmp;
-  if (f.nnz > 0)
-    transpose_csr_device(d_ptr.ptr, X.idx.ptr, X.val.ptr, f.n_users, f.n_items, f.nnz, Xt.idx.ptr, Xt.val.ptr,
-                         col_count, tmp, s);
-  std::vector<int32_t> t_ptr(static_cast<size_t>(f.n_items) + 1, 0);
-  for (int64_t c = 0; c < f.n_items; c++) t_ptr[c + 1] = t_ptr[c] + col_count[c];
-  tsvd::build_segments(h_ptr, X);
-  tsvd::build_segments(t_ptr, Xt);
-  f.spmm_partial.alloc(static_cast<size_t>(std::max<int64_t>(1, std::max(X.n_slot, Xt.n_slot)) * f.k_pad));
+  sblock::upload_with_transpose(h_ptr, indices, data, f.n_users, f.n_items, f.nnz, f.X, f.Xt, f.spmm_partial, f.k_pad,
+                                s);
   IRS_HIP(hipStreamSynchronize(s));  // (h_ptr is the source of an asynchronous copy)
-}
-
-template <int LPR, int NCH>
-static void launch_spmm64(const Csr &M, const float *Q, int l_pad, float *Y, float *partial, hipStream_t s) {
-  hipLaunchKernelGGL((nmf_spmm_kernel<LPR, NCH>), dim3(static_cast<unsigned>(ceil_div(M.n_seg, 4))), dim3(256), 0, s,
-                     static_cast<const int32_t *>(M.seg_row.ptr), static_cast<const int32_t *>(M.seg_begin.ptr),
-                     static_cast<const int32_t *>(M.seg_end.ptr), static_cast<const int32_t *>(M.seg_slot.ptr),
-                     static_cast<int>(M.n_seg), static_cast<const int32_t *>(M.idx.ptr),
-                     static_cast<const float *>(M.val.ptr), Q, l_pad, Y, partial);
 }
 
 // out (M.rows x k_pad) = M in (M.cols x k_pad)
 static void spmm(Fit &f, const Csr &M, const float *in, float *out, hipStream_t s) {
-  Span sp(f, PH_SPMM, s);
-  const int lp = static_cast<int>(f.k_pad), lvec = lp / 4;
+  auto sp = f.spans.span(PH_SPMM, s);
+  const int lp = static_cast<int>(f.k_pad);
   float *partial = f.spmm_partial.ptr;
-  if (lvec == 16) launch_spmm64<16, 1>(M, in, lp, out, partial, s);
-  else if (lvec == 32) launch_spmm64<32, 1>(M, in, lp, out, partial, s);
-  else if (lvec <= 64) launch_spmm64<64, 1>(M, in, lp, out, partial, s);
-  else if (lvec <= 128) launch_spmm64<64, 2>(M, in, lp, out, partial, s);
-  else launch_spmm64<64, 3>(M, in, lp, out, partial, s);
-  if (M.n_split > 0)
-    hipLaunchKernelGGL(tsvd::tsvd_spmm_reduce_kernel, dim3(static_cast<unsigned>(M.n_split)), dim3(256), 0, s,
-                       static_cast<const int32_t *>(M.split_row.ptr), static_cast<const int32_t *>(M.split_first.ptr),
-                       static_cast<const int32_t *>(M.split_count.ptr), static_cast<const float *>(partial), lp, out);
+  sblock::for_spmm_width(lp / 4, [&](auto lpr, auto nch) {
+    sblock::launch_spmm(nmf_spmm_kernel<decltype(lpr)::value, decltype(nch)::value>, M, in, lp, out, partial, s);
+  });
+  sblock::launch_split_reduce(tsvd::tsvd_spmm_reduce_kernel, M, partial, lp, out, s);
   IRS_HIP(hipGetLastError());
   sp.stop();
 }
 
 // G (k_pad x k_pad, symmetric) = B^T B for the block B of `rows` rows, then G[t, t] += l2 for t < k
 static void gram(Fit &f, const float *B, int64_t rows, float l2, hipStream_t s) {
-  Span sp(f, PH_GRAM, s);
-  const int64_t nb = f.k_pad / RIDGE_NB, n_tile = nb * (nb + 1) / 2;
-  const int64_t chunks = std::max<int64_t>(1, ceil_div(rows, RIDGE_NB));
-  const int64_t want_slabs = std::min(chunks, tsvd::gram_slabs(n_tile));
-  const int64_t chunks_per_slab = ceil_div(chunks, want_slabs), n_slab = ceil_div(chunks, chunks_per_slab);
-  hipLaunchKernelGGL(tsvd::tsvd_gram_kernel, dim3(static_cast<unsigned>(n_tile), static_cast<unsigned>(n_slab)),
-                     dim3(256), 0, s, B, static_cast<int>(rows), static_cast<int>(f.k_pad),
-                     static_cast<int>(chunks_per_slab * RIDGE_NB), f.gram_partial.ptr);
-  hipLaunchKernelGGL(nmf_gram_reduce_kernel, dim3(static_cast<unsigned>(n_tile), RIDGE_NB * RIDGE_NB / 256),
-                     dim3(256), 0, s, static_cast<const float *>(f.gram_partial.ptr), static_cast<int>(n_slab),
-                     static_cast<int>(n_tile), static_cast<int>(f.k_pad), f.G.ptr);
+  auto sp = f.spans.span(PH_GRAM, s);
+  const sblock::GramPass pass = sblock::launch_gram_partials(B, rows, f.k_pad, f.gram_partial.ptr, s);
+  hipLaunchKernelGGL(nmf_gram_reduce_kernel, dim3(static_cast<unsigned>(pass.n_tile), RIDGE_NB * RIDGE_NB / 256),
+                     dim3(256), 0, s, static_cast<const float *>(f.gram_partial.ptr), static_cast<int>(pass.n_slab),
+                     static_cast<int>(pass.n_tile), static_cast<int>(f.k_pad), f.G.ptr);
   if (l2 != 0.f)
     hipLaunchKernelGGL(nmf_ridge_kernel, dim3(static_cast<unsigned>(ceil_div(f.k, 64))), dim3(64), 0, s, f.G.ptr,
                        static_cast<int>(f.k), static_cast<int>(f.k_pad), l2);
@@ -138,7 +75,7 @@ static int64_t sweep_groups(int64_t rows) { return ceil_div(rows, SWEEP_ROWS); }
 
 // the rows of Wd swept against G and XH - l1; the workgroups' violation sums go to partial[first ...)
 static void sweep(Fit &f, float *Wd, int64_t rows, float l1, int64_t first, hipStream_t s) {
-  Span sp(f, PH_SWEEP, s);
+  auto sp = f.spans.span(PH_SWEEP, s);
   hipLaunchKernelGGL(nmf_sweep_kernel, dim3(static_cast<unsigned>(sweep_groups(rows))), dim3(SWEEP_ROWS), 0, s, Wd,
                      static_cast<const float *>(f.XH.ptr), static_cast<const float *>(f.G.ptr), static_cast<int>(rows),
                      static_cast<int>(f.k), static_cast<int>(f.k_pad), l1, f.partial.ptr + first);
@@ -154,7 +91,7 @@ static void fit(Fit &f, const int64_t *indptr, const int32_t *indices, const flo
                KP = static_cast<size_t>(f.k_pad);
   std::vector<float> h_t(I * KP, 0.f);  // H^T, padded
   {
-    Span sp(f, PH_SETUP, s);
+    auto sp = f.spans.span(PH_SETUP, s);
     upload_matrix(f, indptr, indices, data, s);
     for (size_t t = 0; t < K; t++)
       for (size_t i = 0; i < I; i++) h_t[i * KP + t] = H[t * I + i];
@@ -166,7 +103,7 @@ static void fit(Fit &f, const int64_t *indptr, const int32_t *indices, const flo
     f.XH.alloc(std::max(U, I) * KP);
     f.G.alloc(KP * KP);
     const int64_t nb = f.k_pad / RIDGE_NB, n_tile = nb * (nb + 1) / 2;
-    f.gram_partial.alloc(static_cast<size_t>(tsvd::gram_slabs(n_tile) * n_tile * RIDGE_NB * RIDGE_NB));
+    f.gram_partial.alloc(static_cast<size_t>(sblock::gram_slabs(n_tile) * n_tile * RIDGE_NB * RIDGE_NB));
     f.partial.alloc(static_cast<size_t>(sweep_groups(f.n_users) + sweep_groups(f.n_items)));
     f.violation.alloc(1);
     sp.stop();
@@ -191,7 +128,7 @@ static void fit(Fit &f, const int64_t *indptr, const int32_t *indices, const flo
     }
     double violation = 0.0;
     {
-      Span sp(f, PH_D2H, s);
+      auto sp = f.spans.span(PH_D2H, s);
       hipLaunchKernelGGL(nmf_violation_kernel, dim3(1), dim3(256), 0, s, static_cast<const double *>(f.partial.ptr),
                          static_cast<int>(groups_W + groups_H), f.violation.ptr);
       IRS_HIP(hipGetLastError());
@@ -199,7 +136,7 @@ static void fit(Fit &f, const int64_t *indptr, const int32_t *indices, const flo
       sp.stop();
     }
     IRS_HIP(hipStreamSynchronize(s));
-    fold_events(f);
+    f.spans.fold();
     n_iter = it;
     if (violations != nullptr) violations[it - 1] = violation;
     // sklearn's test, _fit_coordinate_descent
@@ -208,14 +145,14 @@ static void fit(Fit &f, const int64_t *indptr, const int32_t *indices, const flo
     if (violation / violation_init <= tol) break;
   }
   {
-    Span sp(f, PH_D2H, s);
+    auto sp = f.spans.span(PH_D2H, s);
     IRS_HIP(hipMemcpy2DAsync(W, K * sizeof(float), f.W.ptr, KP * sizeof(float), K * sizeof(float), U,
                              hipMemcpyDeviceToHost, s));
     if (update_H) IRS_HIP(hipMemcpyAsync(h_t.data(), f.Ht.ptr, I * KP * sizeof(float), hipMemcpyDeviceToHost, s));
     sp.stop();
   }
   IRS_HIP(hipStreamSynchronize(s));
-  fold_events(f);
+  f.spans.fold();
   if (update_H)
     for (size_t t = 0; t < K; t++)
       for (size_t i = 0; i < I; i++) H[t * I + i] = h_t[i * KP + t];
@@ -234,12 +171,10 @@ irs_status irs_nmf_fit(int64_t n_users, int64_t n_items, const int64_t *indptr, 
                        float l2_H, double tol, int64_t max_iter, int32_t update_H, int32_t device, int64_t *n_iter,
                        double *violations, irs_nmf_stats_t *stats) {
   return guard([&] {
-    const int64_t nnz = slim::validate_csr(n_users, n_items, indptr, indices, data);
-    check_arg(n_users >= 1 && n_items >= 1, "the matrix must have at least one row and one column.");
-    for (int64_t q = 0; q < nnz; q++) check_arg(std::isfinite(data[q]), "the matrix holds a non-finite value.");
+    const int64_t nnz = validate_finite_matrix(n_users, n_items, indptr, indices, data);
     for (int64_t q = 0; q < nnz; q++) check_arg(data[q] >= 0.f, "the matrix holds a negative value.");
     check_arg(k >= 1, "k must be >= 1.");
-    check_arg(k <= tsvd::MAX_L_PAD, "k must be <= 576.");
+    check_arg(k <= sblock::MAX_L_PAD, "k must be <= 576.");
     check_arg(max_iter >= 1, "max_iter must be >= 1.");
     check_arg(tol >= 0.0, "tol must be >= 0.");
     for (float r : {l1_W, l2_W, l1_H, l2_H})
@@ -254,15 +189,15 @@ irs_status irs_nmf_fit(int64_t n_users, int64_t n_items, const int64_t *indptr, 
     nmf::Fit f;
     f.n_users = n_users, f.n_items = n_items, f.nnz = nnz, f.k = k;
     f.k_pad = ceil_div(k, tsvd::RIDGE_NB) * tsvd::RIDGE_NB;
-    f.timed = stats != nullptr;
+    f.spans.enabled = stats != nullptr;
     nmf::fit(f, indptr, indices, data, W, H, l1_W, l2_W, l1_H, l2_H, tol, max_iter, update_H != 0, n_iter,
              violations);
     if (stats != nullptr) {
-      stats->setup_ms = f.ms[nmf::PH_SETUP];
-      stats->spmm_ms = f.ms[nmf::PH_SPMM];
-      stats->gram_ms = f.ms[nmf::PH_GRAM];
-      stats->sweep_ms = f.ms[nmf::PH_SWEEP];
-      stats->d2h_ms = f.ms[nmf::PH_D2H];
+      stats->setup_ms = f.spans.ms[nmf::PH_SETUP];
+      stats->spmm_ms = f.spans.ms[nmf::PH_SPMM];
+      stats->gram_ms = f.spans.ms[nmf::PH_GRAM];
+      stats->sweep_ms = f.spans.ms[nmf::PH_SWEEP];
+      stats->d2h_ms = f.spans.ms[nmf::PH_D2H];
     }
   });
 }

@@ -6,7 +6,9 @@
 #include <mutex>
 
 #include "common.hpp"
+#include "csr_checks.hpp"
 #include "gram_setup.hpp"
+#include "phase_spans.hpp"
 #include "slim_kernels.hpp"
 
 struct irs_slim_result {
@@ -171,7 +173,7 @@ irs_status irs_slim_fit(int64_t rows, int64_t cols, const int64_t *indptr, const
     check_arg(n_iter > 0, "n_iter must be > 0.");
     check_arg(l2_coeff >= 0, "l2_coeff must be > 0.");
     check_arg(l1_coeff >= 0, "l1_coeff must be > 0.");
-    slim::validate_csr(rows, cols, indptr, indices, data);
+    validate_csr(rows, cols, indptr, indices, data);
     auto res = std::make_unique<irs_slim_result>();
     slim::fit(rows, cols, indptr, indices, data, positive_only != 0, n_iter, l2_coeff, l1_coeff, tol, top_k, device,
               *res);

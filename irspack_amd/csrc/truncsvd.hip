@@ -20,14 +20,19 @@
 #include <cmath>
 #include <numeric>
 
-#include "gram_setup.hpp"
+#include "csr_checks.hpp"
 #include "nmf_kernels.hpp"
-#include "tri_inv_kernels.hpp"
+#include "phase_spans.hpp"
+#include "sparse_block.hpp"
+#include "tile_solver_calls.hpp"
 #include "truncsvd_kernels.hpp"
-#include "truncsvd_plan.hpp"
 
 namespace irs {
 namespace tsvd {
+
+using sblock::Csr;
+using sblock::MAX_L_PAD;
+static_assert(sblock::SEG_LEN == SPMM_SEG && sblock::TILE_EDGE == RIDGE_NB, "sparse_block_plan.hpp's constants");
 
 enum Phase { PH_SPMM = 0, PH_GRAM, PH_CHOL, PH_APPLY, PH_D2H, PH_SETUP, PH_COUNT };
 
@@ -47,64 +52,20 @@ struct Handle {
   DeviceBuffer<float> buf[3], G, W, Ms, gram_partial, spmm_partial;
   DeviceBuffer<int32_t> flag;
   float *Y = nullptr, *Q = nullptr, *S = nullptr;
-  // phase timing: event pairs of the running call, folded into `ms` after its synchronisation
-  std::vector<std::unique_ptr<slim::Event>> ev;
-  std::vector<int> ev_phase;
-  double ms[PH_COUNT] = {0, 0, 0, 0, 0, 0};
+  PhaseSpans<PH_COUNT> spans;  // always recording: the running call's pairs, folded after its synchronisation
   double host_ms = 0.0;  // finish: signs and transpose on the host
   int64_t n_spmm = 0;
 };
 
-struct Span {
-  Handle &h;
-  hipStream_t s;
-  Span(Handle &h_, int phase, hipStream_t s_) : h(h_), s(s_) {
-    h.ev.emplace_back(new slim::Event());
-    h.ev_phase.push_back(phase);
-    IRS_HIP(hipEventRecord(h.ev.back()->e, s));
-  }
-  void stop() {
-    h.ev.emplace_back(new slim::Event());
-    h.ev_phase.push_back(-1);
-    IRS_HIP(hipEventRecord(h.ev.back()->e, s));
-  }
-};
-
-static void begin_call(Handle &h) {
-  h.ev.clear();
-  h.ev_phase.clear();
-}
-
-static void fold_events(Handle &h) {
-  for (size_t i = 0; i + 1 < h.ev.size(); i += 2) h.ms[h.ev_phase[i]] += slim::elapsed_ms(*h.ev[i], *h.ev[i + 1]);
-  h.ev.clear();
-  h.ev_phase.clear();
-}
-
 static void ensure_on_device(Handle &h, hipStream_t s) {
   require_device(h.device);
   if (h.on_device) return;
-  Span sp(h, PH_SETUP, s);
-  Csr &X = h.X, &Xt = h.Xt;
-  X.rows = h.n_users, X.cols = h.n_items, Xt.rows = h.n_items, Xt.cols = h.n_users;
-  DeviceBuffer<int32_t> d_ptr;
-  d_ptr.upload(h.h_ptr, s);
-  X.idx.upload(h.h_idx.data(), static_cast<size_t>(h.nnz), s);
-  X.val.upload(h.h_val.data(), static_cast<size_t>(h.nnz), s);
-  Xt.idx.alloc(static_cast<size_t>(h.nnz));
-  Xt.val.alloc(static_cast<size_t>(h.nnz));
-  std::vector<int32_t> col_count;
-  DeviceBuffer<char> tmp;
-  transpose_csr_device(d_ptr.ptr, X.idx.ptr, X.val.ptr, h.n_users, h.n_items, h.nnz, Xt.idx.ptr, Xt.val.ptr,
-                       col_count, tmp, s);
-  std::vector<int32_t> t_ptr(static_cast<size_t>(h.n_items) + 1, 0);
-  for (int64_t f = 0; f < h.n_items; f++) t_ptr[f + 1] = t_ptr[f] + col_count[f];
-  build_segments(h.h_ptr, X);
-  build_segments(t_ptr, Xt);
-  h.spmm_partial.alloc(static_cast<size_t>(std::max<int64_t>(1, std::max(X.n_slot, Xt.n_slot)) * MAX_L_PAD));
+  auto sp = h.spans.span(PH_SETUP, s);
+  sblock::upload_with_transpose(h.h_ptr, h.h_idx.data(), h.h_val.data(), h.n_users, h.n_items, h.nnz, h.X, h.Xt,
+                                h.spmm_partial, MAX_L_PAD, s);
   h.flag.alloc(1);
-  h.A = h.transposed ? &Xt : &X;
-  h.At = h.transposed ? &X : &Xt;
+  h.A = h.transposed ? &h.Xt : &h.X;
+  h.At = h.transposed ? &h.X : &h.Xt;
   sp.stop();
   h.on_device = true;
   h.h_idx = std::vector<int32_t>();
@@ -114,18 +75,13 @@ static void ensure_on_device(Handle &h, hipStream_t s) {
 // out (M.rows x l_pad) = M in (M.cols x l_pad)
 static void spmm(Handle &h, const Csr &M, const float *in, float *out, hipStream_t s) {
   if (M.rows == 0) return;
-  Span sp(h, PH_SPMM, s);
-  const int lp = static_cast<int>(h.l_pad), lvec = lp / 4;
+  auto sp = h.spans.span(PH_SPMM, s);
+  const int lp = static_cast<int>(h.l_pad);
   float *partial = h.spmm_partial.ptr;
-  if (lvec == 16) launch_spmm<16, 1>(M, in, lp, out, partial, s);
-  else if (lvec == 32) launch_spmm<32, 1>(M, in, lp, out, partial, s);
-  else if (lvec <= 64) launch_spmm<64, 1>(M, in, lp, out, partial, s);
-  else if (lvec <= 128) launch_spmm<64, 2>(M, in, lp, out, partial, s);
-  else launch_spmm<64, 3>(M, in, lp, out, partial, s);
-  if (M.n_split > 0)
-    hipLaunchKernelGGL(tsvd_spmm_reduce_kernel, dim3(static_cast<unsigned>(M.n_split)), dim3(256), 0, s,
-                       static_cast<const int32_t *>(M.split_row.ptr), static_cast<const int32_t *>(M.split_first.ptr),
-                       static_cast<const int32_t *>(M.split_count.ptr), static_cast<const float *>(partial), lp, out);
+  sblock::for_spmm_width(lp / 4, [&](auto lpr, auto nch) {
+    sblock::launch_spmm(tsvd_spmm_kernel<decltype(lpr)::value, decltype(nch)::value>, M, in, lp, out, partial, s);
+  });
+  sblock::launch_split_reduce(tsvd_spmm_reduce_kernel, M, partial, lp, out, s);
   IRS_HIP(hipGetLastError());
   sp.stop();
   h.n_spmm++;
@@ -133,18 +89,11 @@ static void spmm(Handle &h, const Csr &M, const float *in, float *out, hipStream
 
 // G (l_pad x l_pad, symmetric) = B^T B for the block B of `rows` rows
 static void gram(Handle &h, const float *B, int64_t rows, hipStream_t s) {
-  Span sp(h, PH_GRAM, s);
-  const int64_t nb = h.l_pad / RIDGE_NB, n_tile = nb * (nb + 1) / 2;
-  const int64_t chunks = std::max<int64_t>(1, ceil_div(rows, RIDGE_NB));
-  const int64_t want_slabs = std::min(chunks, gram_slabs(n_tile));
-  const int64_t chunks_per_slab = ceil_div(chunks, want_slabs), n_slab = ceil_div(chunks, chunks_per_slab);
-  hipLaunchKernelGGL(tsvd_gram_kernel, dim3(static_cast<unsigned>(n_tile), static_cast<unsigned>(n_slab)), dim3(256),
-                     0, s, B, static_cast<int>(rows), static_cast<int>(h.l_pad),
-                     static_cast<int>(chunks_per_slab * RIDGE_NB), h.gram_partial.ptr);
-  hipLaunchKernelGGL(tsvd_gram_reduce_kernel, dim3(static_cast<unsigned>(n_tile), RIDGE_NB * RIDGE_NB / 256),
-                     dim3(256), 0, s,
-                     static_cast<const float *>(h.gram_partial.ptr), static_cast<int>(n_slab),
-                     static_cast<int>(n_tile), static_cast<int>(h.l_pad), h.G.ptr);
+  auto sp = h.spans.span(PH_GRAM, s);
+  const sblock::GramPass pass = sblock::launch_gram_partials(B, rows, h.l_pad, h.gram_partial.ptr, s);
+  hipLaunchKernelGGL(tsvd_gram_reduce_kernel, dim3(static_cast<unsigned>(pass.n_tile), RIDGE_NB * RIDGE_NB / 256),
+                     dim3(256), 0, s, static_cast<const float *>(h.gram_partial.ptr), static_cast<int>(pass.n_slab),
+                     static_cast<int>(pass.n_tile), static_cast<int>(h.l_pad), h.G.ptr);
   IRS_HIP(hipGetLastError());
   sp.stop();
 }
@@ -153,7 +102,7 @@ static void gram(Handle &h, const float *B, int64_t rows, hipStream_t s) {
 template <bool TRANS>
 static void apply(Handle &h, const float *B, int64_t rows, const float *M, float *out, hipStream_t s) {
   if (rows == 0) return;
-  Span sp(h, PH_APPLY, s);
+  auto sp = h.spans.span(PH_APPLY, s);
   hipLaunchKernelGGL((tsvd_apply_kernel<TRANS>),
                      dim3(static_cast<unsigned>(ceil_div(rows, RIDGE_NB)), static_cast<unsigned>(h.l_pad / RIDGE_NB)),
                      dim3(256), 0, s, B, static_cast<int>(rows), static_cast<int>(h.l_pad), M, out);
@@ -165,33 +114,14 @@ static void apply(Handle &h, const float *B, int64_t rows, const float *M, float
 static void normalise(Handle &h, const float *B, int64_t rows, hipStream_t s) {
   gram(h, B, rows, s);
   {
-    Span sp(h, PH_CHOL, s);
+    auto sp = h.spans.span(PH_CHOL, s);
     const int lp = static_cast<int>(h.l_pad);
     const int64_t nb = h.l_pad / RIDGE_NB;
     float *G = h.G.ptr, *W = h.W.ptr;
     hipLaunchKernelGGL(tsvd_shift_kernel, dim3(1), dim3(64), 0, s, G, static_cast<int>(h.l), lp);
-    for (int64_t k = 0; k < nb; k++) {
-      hipLaunchKernelGGL(ials::ridge_chol_diag_kernel, dim3(1), dim3(256), 0, s, G, lp, static_cast<int>(k),
-                         h.flag.ptr);
-      const int64_t below = h.l_pad - (k + 1) * RIDGE_NB, t = nb - k - 1;
-      if (below <= 0) continue;
-      hipLaunchKernelGGL(ials::ridge_chol_trsm_kernel, dim3(static_cast<unsigned>(ceil_div(below, 256))), dim3(256),
-                         0, s, G, lp, static_cast<int>(k));
-      hipLaunchKernelGGL(ials::ridge_chol_update_kernel, dim3(static_cast<unsigned>(t * (t + 1) / 2)), dim3(256), 0,
-                         s, G, lp, static_cast<int>(k));
-    }
+    launch_tile_cholesky(G, lp, nb, h.flag.ptr, s);
     h.W.zero(s);
-    hipLaunchKernelGGL(dslim::dslim_diag_inv_kernel, dim3(static_cast<unsigned>(nb)), dim3(64), 0, s,
-                       static_cast<const float *>(G), lp, W);
-    for (int64_t k = 0; k < nb; k++) {
-      if (k > 0)
-        hipLaunchKernelGGL(dslim::dslim_inv_row_kernel, dim3(static_cast<unsigned>(k)), dim3(256), 0, s, W, lp,
-                           static_cast<int>(k));
-      if (k + 1 < nb)
-        hipLaunchKernelGGL(dslim::dslim_inv_update_kernel,
-                           dim3(static_cast<unsigned>(nb - k - 1), static_cast<unsigned>(k + 1)), dim3(256), 0, s,
-                           static_cast<const float *>(G), W, lp, static_cast<int>(k));
-    }
+    launch_tile_tri_inverse(G, W, lp, nb, s);
     IRS_HIP(hipGetLastError());
     sp.stop();
   }
@@ -201,14 +131,14 @@ static void normalise(Handle &h, const float *B, int64_t rows, hipStream_t s) {
 // the leading l x l block of G into the caller's array, then the call's one synchronisation
 static void gram_home_and_sync(Handle &h, float *gram_out, hipStream_t s) {
   {
-    Span sp(h, PH_D2H, s);
+    auto sp = h.spans.span(PH_D2H, s);
     IRS_HIP(hipMemcpy2DAsync(gram_out, static_cast<size_t>(h.l) * sizeof(float), h.G.ptr,
                              static_cast<size_t>(h.l_pad) * sizeof(float), static_cast<size_t>(h.l) * sizeof(float),
                              static_cast<size_t>(h.l), hipMemcpyDeviceToHost, s));
     sp.stop();
   }
   IRS_HIP(hipStreamSynchronize(s));
-  fold_events(h);
+  h.spans.fold();
 }
 
 static void range(Handle &h, const float *omega, int64_t rows, int64_t l, int64_t n_iter, float *gram_out) {
@@ -220,7 +150,7 @@ static void range(Handle &h, const float *omega, int64_t rows, int64_t l, int64_
   check_arg(omega != nullptr && gram_out != nullptr, "omega and gram_out must not be null.");
   for (int64_t i = 0; i < rows * l; i++) check_arg(std::isfinite(omega[i]), "omega must be finite.");
   hipStream_t s = nullptr;
-  begin_call(h);
+  h.spans.clear();
   ensure_on_device(h, s);
   h.l = l;
   h.l_pad = ceil_div(l, RIDGE_NB) * RIDGE_NB;
@@ -232,7 +162,7 @@ static void range(Handle &h, const float *omega, int64_t rows, int64_t l, int64_
   size_t have = 0;
   for (auto &b : h.buf) have += b.count >= block ? block : 0;
   const int64_t nb = h.l_pad / RIDGE_NB, n_tile = nb * (nb + 1) / 2;
-  const size_t partials = static_cast<size_t>(gram_slabs(n_tile) * n_tile * RIDGE_NB * RIDGE_NB);
+  const size_t partials = static_cast<size_t>(sblock::gram_slabs(n_tile) * n_tile * RIDGE_NB * RIDGE_NB);
   const double need = 4.0 * double(3 * block - have) + 12.0 * double(LP2) + 4.0 * double(partials) +
                       double(size_t(64) << 20);
   if (need > double(free_b))
@@ -283,7 +213,7 @@ static void apply_host(Handle &h, const float *M, int64_t l2, float *gram_out) {
   check_arg(M != nullptr && gram_out != nullptr, "m and gram_out must not be null.");
   for (int64_t i = 0; i < h.l * l2; i++) check_arg(std::isfinite(M[i]), "m must be finite.");
   hipStream_t s = nullptr;
-  begin_call(h);
+  h.spans.clear();
   require_device(h.device);
   upload_small(h, M, h.l, l2, s);
   apply<false>(h, h.Y, h.m, h.Ms.ptr, h.S, s);
@@ -298,7 +228,7 @@ static void project(Handle &h, float *gram_out) {
   check_arg(h.l >= 1 && h.Y != nullptr, "irs_truncsvd_range has not run.");
   check_arg(gram_out != nullptr, "gram_out must not be null.");
   hipStream_t s = nullptr;
-  begin_call(h);
+  h.spans.clear();
   require_device(h.device);
   spmm(h, *h.At, h.Y, h.Q, s);
   gram(h, h.Q, h.n, s);
@@ -313,7 +243,7 @@ static void finish(Handle &h, const float *rot, int64_t k, float *z_out, float *
   check_arg(rot != nullptr && z_out != nullptr && components_out != nullptr, "null argument.");
   for (int64_t i = 0; i < h.l * k; i++) check_arg(std::isfinite(rot[i]), "rot must be finite.");
   hipStream_t s = nullptr;
-  begin_call(h);
+  h.spans.clear();
   require_device(h.device);
   upload_small(h, rot, h.l, k, s);
   // V, n_items x k: rows of Q when A = X (B^T R / sigma), rows of Y when A = X^T (Y R); z = X V
@@ -331,7 +261,7 @@ static void finish(Handle &h, const float *rot, int64_t k, float *z_out, float *
   const size_t I = static_cast<size_t>(h.n_items), U = static_cast<size_t>(h.n_users), K = static_cast<size_t>(k);
   std::vector<float> V(I * K);
   {
-    Span sp(h, PH_D2H, s);
+    auto sp = h.spans.span(PH_D2H, s);
     IRS_HIP(hipMemcpy2DAsync(V.data(), K * sizeof(float), h.S, static_cast<size_t>(h.l_pad) * sizeof(float),
                              K * sizeof(float), I, hipMemcpyDeviceToHost, s));
     IRS_HIP(hipMemcpy2DAsync(z_out, K * sizeof(float), z_dev, static_cast<size_t>(h.l_pad) * sizeof(float),
@@ -339,7 +269,7 @@ static void finish(Handle &h, const float *rot, int64_t k, float *z_out, float *
     sp.stop();
   }
   IRS_HIP(hipStreamSynchronize(s));
-  fold_events(h);
+  h.spans.fold();
   // svd_flip(u_based_decision=False): the entry of largest magnitude of every component (the first of equals)
   // is positive; the components go out transposed
   const auto t0 = std::chrono::steady_clock::now();
@@ -374,9 +304,7 @@ irs_status irs_truncsvd_create(int64_t n_users, int64_t n_items, const int64_t *
   return guard([&] {
     check_arg(out != nullptr, "out must not be null.");
     *out = nullptr;
-    const int64_t nnz = slim::validate_csr(n_users, n_items, indptr, indices, data);
-    check_arg(n_users >= 1 && n_items >= 1, "the matrix must have at least one row and one column.");
-    for (int64_t q = 0; q < nnz; q++) check_arg(std::isfinite(data[q]), "the matrix holds a non-finite value.");
+    const int64_t nnz = validate_finite_matrix(n_users, n_items, indptr, indices, data);
     check_arg(device >= 0, "irspack_amd: device index out of range.");
     std::unique_ptr<irs_truncsvd> p(new irs_truncsvd());
     tsvd::Handle &h = p->h;
@@ -425,12 +353,12 @@ irs_status irs_truncsvd_stats(irs_truncsvd *t, irs_truncsvd_stats_t *out) {
   return guard([&] {
     check_arg(t != nullptr && out != nullptr, "null argument.");
     const tsvd::Handle &h = t->h;
-    out->setup_ms = h.ms[tsvd::PH_SETUP];
-    out->spmm_ms = h.ms[tsvd::PH_SPMM];
-    out->gram_ms = h.ms[tsvd::PH_GRAM];
-    out->chol_ms = h.ms[tsvd::PH_CHOL];
-    out->apply_ms = h.ms[tsvd::PH_APPLY];
-    out->d2h_ms = h.ms[tsvd::PH_D2H];
+    out->setup_ms = h.spans.ms[tsvd::PH_SETUP];
+    out->spmm_ms = h.spans.ms[tsvd::PH_SPMM];
+    out->gram_ms = h.spans.ms[tsvd::PH_GRAM];
+    out->chol_ms = h.spans.ms[tsvd::PH_CHOL];
+    out->apply_ms = h.spans.ms[tsvd::PH_APPLY];
+    out->d2h_ms = h.spans.ms[tsvd::PH_D2H];
     out->host_ms = h.host_ms;
     out->n_spmm = h.n_spmm;
     out->l_pad = h.l_pad;
@@ -448,7 +376,7 @@ irs_status irs_truncsvd_transform(int64_t rows, int64_t n_items, const int64_t *
                                   const float *data, int64_t k, const float *item_factors, int32_t device,
                                   float *out) {
   return guard([&] {
-    const int64_t nnz = slim::validate_csr(rows, n_items, indptr, indices, data);
+    const int64_t nnz = validate_csr(rows, n_items, indptr, indices, data);
     check_arg(n_items >= 1, "the matrix must have at least one column.");
     for (int64_t q = 0; q < nnz; q++) check_arg(std::isfinite(data[q]), "the matrix holds a non-finite value.");
     check_arg(k >= 1 && k <= tsvd::MAX_L_PAD, "k must lie in 1 .. 576.");
@@ -465,7 +393,7 @@ irs_status irs_truncsvd_transform(int64_t rows, int64_t n_items, const int64_t *
     for (int64_t i = 0; i <= rows; i++) h_ptr[i] = static_cast<int32_t>(indptr[i]);
     X.idx.upload(indices, static_cast<size_t>(nnz), s);
     X.val.upload(data, static_cast<size_t>(nnz), s);
-    tsvd::build_segments(h_ptr, X);
+    sblock::upload_segments(h_ptr, X);
     DeviceBuffer<float> V, Z;
     DeviceBuffer<double> partial;
     V.alloc(static_cast<size_t>(n_items) * KP);
@@ -474,25 +402,12 @@ irs_status irs_truncsvd_transform(int64_t rows, int64_t n_items, const int64_t *
                              static_cast<size_t>(n_items), hipMemcpyHostToDevice, s));
     Z.alloc(static_cast<size_t>(rows) * KP);
     partial.alloc(static_cast<size_t>(std::max<int64_t>(1, X.n_slot)) * KP);
-    const int lp = static_cast<int>(k_pad), lvec = lp / 4;
-    auto launch = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(ceil_div(X.n_seg, 4))), dim3(256), 0, s,
-                         static_cast<const int32_t *>(X.seg_row.ptr), static_cast<const int32_t *>(X.seg_begin.ptr),
-                         static_cast<const int32_t *>(X.seg_end.ptr), static_cast<const int32_t *>(X.seg_slot.ptr),
-                         static_cast<int>(X.n_seg), static_cast<const int32_t *>(X.idx.ptr),
-                         static_cast<const float *>(X.val.ptr), static_cast<const float *>(V.ptr), lp, Z.ptr,
-                         partial.ptr);
-    };
-    if (lvec == 16) launch(nmf::nmf_spmm_kernel<16, 1, double>);
-    else if (lvec == 32) launch(nmf::nmf_spmm_kernel<32, 1, double>);
-    else if (lvec <= 64) launch(nmf::nmf_spmm_kernel<64, 1, double>);
-    else if (lvec <= 128) launch(nmf::nmf_spmm_kernel<64, 2, double>);
-    else launch(nmf::nmf_spmm_kernel<64, 3, double>);
-    if (X.n_split > 0)
-      hipLaunchKernelGGL(nmf::nmf_spmm_reduce_f64_kernel, dim3(static_cast<unsigned>(X.n_split)), dim3(256), 0, s,
-                         static_cast<const int32_t *>(X.split_row.ptr), static_cast<const int32_t *>(X.split_first.ptr),
-                         static_cast<const int32_t *>(X.split_count.ptr), static_cast<const double *>(partial.ptr), lp,
-                         Z.ptr);
+    const int lp = static_cast<int>(k_pad);
+    sblock::for_spmm_width(lp / 4, [&](auto lpr, auto nch) {
+      sblock::launch_spmm(nmf::nmf_spmm_kernel<decltype(lpr)::value, decltype(nch)::value, double>, X, V.ptr, lp,
+                          Z.ptr, partial.ptr, s);
+    });
+    sblock::launch_split_reduce(nmf::nmf_spmm_reduce_f64_kernel, X, partial.ptr, lp, Z.ptr, s);
     IRS_HIP(hipGetLastError());
     IRS_HIP(hipMemcpy2DAsync(out, K * sizeof(float), Z.ptr, KP * sizeof(float), K * sizeof(float),
                              static_cast<size_t>(rows), hipMemcpyDeviceToHost, s));

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../irspack_amd/csrc/bpr_host_prep.hpp"
+#include "../../irspack_amd/csrc/csr_checks.hpp"
 
 using namespace irs;
 using namespace irs::bpr;
@@ -57,7 +58,7 @@ static Matrix small_matrix() {
 
 static void test_filter_and_sampling() {
   const Matrix m = small_matrix();
-  CHECK(validate_matrix(m.rows, m.cols, m.indptr.data(), m.indices.data(), m.data.data()) == 15);
+  CHECK(validate_finite_matrix(m.rows, m.cols, m.indptr.data(), m.indices.data(), m.data.data()) == 15);
   const Positives p = filter_positives(m.rows, m.cols, m.indptr.data(), m.indices.data(), m.data.data());
   CHECK(p.n_positives == 13 && p.n_skipped_rows == 1 && p.n_skipped_positives == 5);
   CHECK((p.indptr == std::vector<int32_t>{0, 2, 2, 7, 11, 11, 13}));
@@ -134,7 +135,7 @@ static void test_unseen_rank() {
 static void test_checks() {
   const Matrix m = small_matrix();
   auto run = [&](const Matrix &x) {
-    return message_of([&] { validate_matrix(x.rows, x.cols, x.indptr.data(), x.indices.data(), x.data.data()); });
+    return message_of([&] { validate_finite_matrix(x.rows, x.cols, x.indptr.data(), x.indices.data(), x.data.data()); });
   };
   CHECK(run(m).empty());
   Matrix bad = m;

@@ -14,6 +14,9 @@ available on the pool; this covers the code that runs on host threads:
 - tests/host/ials_host_plan_main.cpp: ials_host_plan.hpp, i.e. what the iALS path decides on the host - the task plan
   of a side (chunks, fold groups, the short tail, the row classes) and the route of a half-step (kernel family and
   instance flags, against the former chains of conditions).
+- tests/host/sparse_block_plan_main.cpp: sparse_block_plan.hpp and csr_checks.hpp, i.e. what the truncated SVD and
+  the NMF fit decide on the host - the segment plan of a matrix, the slabs of a Gram pass, the width of a product
+  kernel (against the former code, written out) - and the checks of a caller's CSR matrix, message by message.
 The stream, event and buffer handling of knn.hip itself needs a device and is not compiled here."""
 import os
 import shutil
@@ -202,3 +205,33 @@ def test_ials_host_plan_plain_optimised_build(tmp_path):
     r = _ials_host_plan(tmp_path, ["-O3"], {})
     assert r.returncode == 0, r.stderr[-4000:]
     assert "ials_host_plan ok" in r.stdout
+
+
+def _sparse_block_plan(tmp_path, flags):
+    exe = str(tmp_path / "sparse_block_plan_main")
+    src = os.path.join(ROOT, "tests", "host", "sparse_block_plan_main.cpp")
+    subprocess.check_call([_HOST_CXX, "-std=c++17", "-pthread", *flags, src, "-o", exe])
+    return subprocess.run([exe], capture_output=True, text=True, timeout=600)
+
+
+@pytest.mark.skipif(_HOST_CXX is None, reason="needs a host C++ compiler")
+def test_sparse_block_plan_under_address_and_ub_sanitizers(tmp_path):
+    """irspack_amd/csrc/sparse_block_plan.hpp - the segment plan at row lengths round the segment length (split rows,
+    their consecutive slots, the stable longest-first order, empty and zero-row matrices), the slabs of a Gram pass
+    and the width of a product kernel against the former code, written out - and csr_checks.hpp - every message at
+    its first failing condition, their precedence, null arrays at nnz = 0, zero rows - in a program of its own
+    (tests/host/sparse_block_plan_main.cpp), every report fatal."""
+    r = _sparse_block_plan(tmp_path, ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                                      "-fno-omit-frame-pointer"])
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+    assert "sparse_block_plan ok" in r.stdout
+
+
+@pytest.mark.skipif(_HOST_CXX is None, reason="needs a host C++ compiler")
+def test_sparse_block_plan_plain_optimised_build(tmp_path):
+    """The same program without a sanitizer at -O3 with the library's -ffp-contract=off: the build whose integer
+    divisions run as the library runs them."""
+    r = _sparse_block_plan(tmp_path, ["-O3", "-ffp-contract=off"])
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert "sparse_block_plan ok" in r.stdout

@@ -70,7 +70,7 @@ def test_small_inputs():
 
 def gram_plan(rows, l_pad):
     """``(chunks of 64 rows, chunks per slab, slabs, live rows of the last chunk)`` of a Gram pass, restated from
-    ``gram`` in truncsvd.hip and ``gram_slabs`` in truncsvd_plan.hpp"""
+    ``plan_gram_pass`` and ``gram_slabs`` in sparse_block_plan.hpp"""
     nb = l_pad // 64
     n_tile = nb * (nb + 1) // 2
     chunks = max(1, -(-rows // 64))
