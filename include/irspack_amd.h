@@ -570,6 +570,16 @@ irs_status irs_slim_fetch(irs_slim_result *r, int64_t *col_ptr, int32_t *indices
  * changes applied (one axpy over a column of G each).  Any pointer may be NULL. */
 irs_status irs_slim_last_stats(irs_slim_result *r, double *gram_ms, double *descent_ms,
                                double *emit_ms, int64_t *sweeps_total, int64_t *updates_total);
+/* Measurement only: the launch of the descent kernel in the call that produced the result.  lds_r: 1 when
+ * the running vector of a column lived in LDS, 0 when in a global scratch row per workgroup; lds_bytes: the
+ * dynamic LDS of the launch (400 + 4 cols, or the 400 bytes of slots alone); threads: the workgroup size,
+ * which is the width of a chunk (256 up to 40 KiB of LDS, 512 up to 80 KiB, 1024 above); n_wg: the
+ * persistent workgroups; raise_dynamic_lds: 1 when the launch needed the kernel's dynamic-LDS limit raised
+ * (above 64 KiB); lds_per_block: the per-block LDS limit the device reported (the vector is in LDS while
+ * 400 + 4 cols is at most that and IRSPACK_AMD_SLIM_LDS is not 0).  All 0 after a call that did no device
+ * work (no columns or no entries).  Any pointer may be NULL. */
+irs_status irs_slim_last_launch(irs_slim_result *r, int32_t *lds_r, int32_t *lds_bytes, int32_t *threads,
+                                int32_t *n_wg, int32_t *raise_dynamic_lds, int64_t *lds_per_block);
 irs_status irs_slim_destroy(irs_slim_result *r);
 
 /* ------------------------------------------------------------------ EASE / EDLAE

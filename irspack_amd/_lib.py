@@ -242,6 +242,7 @@ EXPORTED_SYMBOLS = [
     "irs_slim_nnz",
     "irs_slim_fetch",
     "irs_slim_last_stats",
+    "irs_slim_last_launch",
     "irs_slim_destroy",
     "irs_dense_slim_fit",
     "irs_truncsvd_create",
@@ -315,6 +316,8 @@ ARGTYPES = {
     "irs_slim_fetch": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float)],
     "irs_slim_last_stats": [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                             C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "irs_slim_last_launch": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)],
     "irs_slim_destroy": [C.c_void_p],
     "irs_dense_slim_fit": [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float),
                            C.c_float, C.c_float, C.c_int32, C.POINTER(C.c_float), C.c_void_p],

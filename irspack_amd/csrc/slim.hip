@@ -18,6 +18,8 @@ struct irs_slim_result {
   std::vector<float> data;
   double gram_ms = 0.0, descent_ms = 0.0, emit_ms = 0.0;
   int64_t sweeps_total = 0, updates_total = 0;
+  irs::slim::LaunchPlan plan;  // of the descent launch (all zero when the call did no device work)
+  int64_t lds_per_block = 0;   // sharedMemPerBlock as the device reported it
 };
 
 namespace irs {
@@ -51,13 +53,12 @@ static void fit(int64_t rows, int64_t cols, const int64_t *indptr, const int32_t
   const size_t I = static_cast<size_t>(cols);
 
   // where the running vector lives, and the launch shape that follows from it
-  const int lds_need = kSlotBytes + static_cast<int>(std::min<size_t>(I * 4, size_t(1) << 30));
-  const bool lds_r = env_flag("IRSPACK_AMD_SLIM_LDS", true) && I * 4 + kSlotBytes <= prop.sharedMemPerBlock;
-  const int lds_bytes = lds_r ? lds_need : kSlotBytes;
-  // few workgroups fit beside a large LDS image: make each one wide (every wave streams the axpy)
-  const int threads = lds_bytes > 80 * 1024 ? 1024 : lds_bytes > 40 * 1024 ? 512 : 256;
-  const int per_cu = std::max(1, std::min<int>(2048 / threads, static_cast<int>(prop.maxSharedMemoryPerMultiProcessor / std::max(lds_bytes, 1))));
-  const int n_wg = static_cast<int>(std::min<int64_t>(cols, int64_t(prop.multiProcessorCount) * std::min(per_cu, 4)));
+  const LaunchPlan plan = plan_launch(cols, prop.sharedMemPerBlock, prop.maxSharedMemoryPerMultiProcessor,
+                                      prop.multiProcessorCount, env_flag("IRSPACK_AMD_SLIM_LDS", true));
+  const bool lds_r = plan.lds_r;
+  const int lds_bytes = plan.lds_bytes, threads = plan.threads, n_wg = plan.n_wg;
+  res.plan = plan;
+  res.lds_per_block = static_cast<int64_t>(prop.sharedMemPerBlock);
 
   // memory: G and the dense W (4 I^2 bytes each), the matrix twice, the q rows of the global path
   size_t free_b = 0, total_b = 0;
@@ -96,7 +97,7 @@ static void fit(int64_t rows, int64_t cols, const int64_t *indptr, const int32_t
   d_stats.alloc(2);
   d_stats.zero(s);
   auto launch = [&](auto kernel, int which) {
-    if (lds_bytes > 64 * 1024) allow_dynamic_lds(kernel, which, device, static_cast<int>(prop.sharedMemPerBlock));
+    if (plan.raise_dynamic_lds) allow_dynamic_lds(kernel, which, device, static_cast<int>(prop.sharedMemPerBlock));
     hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(n_wg)), dim3(static_cast<unsigned>(threads)),
                        static_cast<size_t>(lds_bytes), s, static_cast<const float *>(d_G.ptr),
                        static_cast<const float *>(d_diag.ptr), static_cast<const int32_t *>(d_order.ptr), n_items,
@@ -209,6 +210,19 @@ irs_status irs_slim_last_stats(irs_slim_result *r, double *gram_ms, double *desc
     if (emit_ms) *emit_ms = r->emit_ms;
     if (sweeps_total) *sweeps_total = r->sweeps_total;
     if (updates_total) *updates_total = r->updates_total;
+  });
+}
+
+irs_status irs_slim_last_launch(irs_slim_result *r, int32_t *lds_r, int32_t *lds_bytes, int32_t *threads,
+                                int32_t *n_wg, int32_t *raise_dynamic_lds, int64_t *lds_per_block) {
+  return guard([&] {
+    check_arg(r != nullptr, "null argument.");
+    if (lds_r) *lds_r = r->plan.lds_r ? 1 : 0;
+    if (lds_bytes) *lds_bytes = r->plan.lds_bytes;
+    if (threads) *threads = r->plan.threads;
+    if (n_wg) *n_wg = r->plan.n_wg;
+    if (raise_dynamic_lds) *raise_dynamic_lds = r->plan.raise_dynamic_lds ? 1 : 0;
+    if (lds_per_block) *lds_per_block = r->lds_per_block;
   });
 }
 

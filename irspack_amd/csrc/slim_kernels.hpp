@@ -7,15 +7,10 @@
 //   count / scan / emit   the dense coefficient rows -> CSC arrays (top_k selection by value)
 #pragma once
 #include "common.hpp"
+#include "slim_host_plan.hpp"  // kMaxWaves, kSlotBytes: the LDS layout the launch decision counts with
 
 namespace irs {
 namespace slim {
-
-constexpr int kMaxWaves = 16;  // waves of a descent workgroup (1024 threads)
-// fixed head of the descent kernel's dynamic LDS (bytes): two buffers of per-wave (ballot, delta) slots
-// and the column handed out by the cursor; the running vector follows it (16-byte aligned, Guideline 17)
-constexpr int kSlotBytes = 2 * kMaxWaves * 8 + 2 * kMaxWaves * 4 + 16;
-static_assert(kSlotBytes % 16 == 0, "the running vector starts 16-byte aligned");
 
 __global__ void gram_diag_kernel(const float *__restrict__ G, int32_t n_items, float *__restrict__ diag) {
   const int f = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);

@@ -166,6 +166,11 @@ def _slim(X, positive_only: bool, n_threads: int, n_iter: int, l2_coeff: float, 
             check(lib().irs_slim_last_stats(handle, C.byref(g), C.byref(d), C.byref(e), C.byref(sw), C.byref(up)))
             stats.update(gram_ms=g.value, descent_ms=d.value, emit_ms=e.value, sweeps_total=sw.value,
                          updates_total=up.value)
+            la = [C.c_int32() for _ in range(5)]
+            limit = C.c_int64()
+            check(lib().irs_slim_last_launch(handle, *[C.byref(v) for v in la], C.byref(limit)))
+            stats.update(lds_r=bool(la[0].value), lds_bytes=la[1].value, threads=la[2].value, n_wg=la[3].value,
+                         raise_dynamic_lds=bool(la[4].value), lds_per_block=limit.value)
     finally:
         lib().irs_slim_destroy(handle)
     W = sps.csc_matrix((vals[:nnz.value], rows[:nnz.value], col_ptr), shape=(n_items, n_items))
@@ -174,7 +179,8 @@ def _slim(X, positive_only: bool, n_threads: int, n_iter: int, l2_coeff: float, 
 
 
 def slim_weight_allow_negative(X, n_threads: int, n_iter: int, l2_coeff: float, l1_coeff: float,
-                               tol: float, top_k: int = -1, *, device: Optional[int] = None) -> sps.csc_matrix:
+                               tol: float, top_k: int = -1, *, device: Optional[int] = None,
+                               stats: Optional[dict] = None) -> sps.csc_matrix:
     """util.hpp:228-424 with ``positive_only = false`` (bound at util.cpp:31-35): for every item ``j`` the
     elastic-net fit of column ``j`` on the other columns, ``min 1/2 |x_j - X w|^2 + l2/2 |w|^2 + l1 |w|_1``,
     by cyclic coordinate descent from 0 on the device (``irs_slim_fit``).  Returns the ``I x I`` float32
@@ -191,14 +197,20 @@ def slim_weight_allow_negative(X, n_threads: int, n_iter: int, l2_coeff: float, 
     * a coordinate with ``G_ff + l2 == 0`` (an item without interactions, ``l2_coeff = 0``) gets 0.
 
     ``top_k >= 0`` keeps the ``top_k`` largest values (not magnitudes) of a column that has more
-    non-zeros; ``-1`` keeps everything.  Duplicate entries of ``X`` are summed first."""
-    return _slim(X, False, n_threads, n_iter, l2_coeff, l1_coeff, tol, top_k, device)
+    non-zeros; ``-1`` keeps everything.  Duplicate entries of ``X`` are summed first.
+
+    ``stats`` (measurement only) receives the phase times ``gram_ms, descent_ms, emit_ms`` (HIP events), the
+    counters ``sweeps_total, updates_total`` and the launch of the descent kernel: ``lds_r`` (the running vector
+    in LDS), ``lds_bytes``, ``threads``, ``n_wg``, ``raise_dynamic_lds`` and the per-block LDS limit the device
+    reported, ``lds_per_block`` (``irs_slim_last_stats``, ``irs_slim_last_launch``)."""
+    return _slim(X, False, n_threads, n_iter, l2_coeff, l1_coeff, tol, top_k, device, stats)
 
 
 def slim_weight_positive_only(X, n_threads: int, n_iter: int, l2_coeff: float, l1_coeff: float,
-                              tol: float, top_k: int = -1, *, device: Optional[int] = None) -> sps.csc_matrix:
+                              tol: float, top_k: int = -1, *, device: Optional[int] = None,
+                              stats: Optional[dict] = None) -> sps.csc_matrix:
     """:func:`slim_weight_allow_negative` under the constraint ``w >= 0`` (util.cpp:36-40)."""
-    return _slim(X, True, n_threads, n_iter, l2_coeff, l1_coeff, tol, top_k, device)
+    return _slim(X, True, n_threads, n_iter, l2_coeff, l1_coeff, tol, top_k, device, stats)
 
 
 def dense_slim_weight(X, reg: float, diag_scale: float = 0.0, *, device: Optional[int] = None,

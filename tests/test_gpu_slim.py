@@ -25,9 +25,9 @@ X_SMALL = sps.csr_matrix(
     np.asarray([[1, 1, 2, 3, 4], [0, 1, 0, 1, 0], [0, 0, 1, 0, 0], [0, 0, 0, 0, 0]], dtype=float))
 
 
-def fit(X, positive_only, l2, l1, n_iter=100, tol=0.0, top_k=-1):
+def fit(X, positive_only, l2, l1, n_iter=100, tol=0.0, top_k=-1, stats=None):
     f = slim_weight_positive_only if positive_only else slim_weight_allow_negative
-    return f(X, 1, n_iter, l2, l1, tol, top_k)
+    return f(X, 1, n_iter, l2, l1, tol, top_k, stats=stats)
 
 
 def coeffs(n_users, alpha, l1_ratio):
@@ -226,15 +226,40 @@ def lds_switch():
 def test_reproducible_and_global_path_identical(positive_only, lds_switch):
     """Two calls: the same bytes.  IRSPACK_AMD_SLIM_LDS=0 (the running vector in global memory): the same
     bytes too - every element of the running vector sees the same operations in the same order on both
-    paths, only where it is kept differs."""
+    paths, only where it is kept differs.  The library reports which path a call took
+    (``irs_slim_last_launch``): the switch flips it, both run 256 threads at this size."""
     X, _, _ = ml100k(True)
     l2, l1 = coeffs(X.shape[0], 1e-3, 0.5)
     os.environ.pop("IRSPACK_AMD_SLIM_LDS", None)
-    A = fit(X, positive_only, l2, l1, 10, 0.0)
+    on, off = {}, {}
+    A = fit(X, positive_only, l2, l1, 10, 0.0, stats=on)
     B = fit(X, positive_only, l2, l1, 10, 0.0)
     assert A.nnz > 0 and same_bytes(A, B)
     os.environ["IRSPACK_AMD_SLIM_LDS"] = "0"
-    assert same_bytes(A, fit(X, positive_only, l2, l1, 10, 0.0))
+    assert same_bytes(A, fit(X, positive_only, l2, l1, 10, 0.0, stats=off))
+    assert on["lds_r"] is True and off["lds_r"] is False
+    assert on["threads"] == 256 and off["threads"] == 256
+    assert on["lds_bytes"] == 400 + 4 * X.shape[1] and off["lds_bytes"] == 400
+    assert (on["sweeps_total"], on["updates_total"]) == (off["sweeps_total"], off["updates_total"])
+
+
+@pytest.mark.parametrize("positive_only", [True, False])
+def test_ml100k_bytes_are_the_recorded_ones(positive_only):
+    """The 256-thread result at the ML-100K shape is held to the bytes recorded before the launch decision moved
+    into slim_host_plan.hpp (tests/golden/slim_ml100k_sha256.json): a change to the descent for the wide
+    shapes must leave this one as it was."""
+    import hashlib
+    import json
+
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "slim_ml100k_sha256.json")) as f:
+        want = json.load(f)[f"positive_only={positive_only}"]
+    X, _, _ = ml100k(True)
+    l2, l1 = coeffs(X.shape[0], 1e-3, 0.5)
+    W = fit(X, positive_only, l2, l1, 10, 0.0)
+    assert W.data.dtype == np.float32
+    got = hashlib.sha256(W.indptr.astype(np.int32).tobytes() + W.indices.astype(np.int32).tobytes()
+                         + W.data.tobytes()).hexdigest()
+    assert (int(W.nnz), got) == (want["nnz"], want["sha256"])
 
 
 # ------------------------------------------------------------------ 7. edges
@@ -279,13 +304,15 @@ def test_above_the_lds_threshold():
     coo = small.tocoo()
     big = sps.csr_matrix((coo.data, (coo.row, touched[coo.col])), shape=(n_users, n_items))
     l2, l1 = 0.5, 0.25
+    stats = {}
     try:
-        W_big = fit(big, False, l2, l1, 4, 0.0)
+        W_big = fit(big, False, l2, l1, 4, 0.0, stats=stats)
     except RuntimeError as exc:
         if "device memory" in str(exc):
             pytest.skip(f"NOT RUN: {exc}")
         raise
     print("test_above_the_lds_threshold: RUN (the device had the memory)")
+    assert stats["lds_r"] is False and stats["threads"] == 256
     W_small = fit(small, False, l2, l1, 4, 0.0)
     assert W_small.nnz > 0 and W_big.nnz == W_small.nnz
     sub = W_big[touched][:, touched].tocsc()

@@ -17,6 +17,9 @@ available on the pool; this covers the code that runs on host threads:
 - tests/host/sparse_block_plan_main.cpp: sparse_block_plan.hpp and csr_checks.hpp, i.e. what the truncated SVD and
   the NMF fit decide on the host - the segment plan of a matrix, the slabs of a Gram pass, the width of a product
   kernel (against the former code, written out) - and the checks of a caller's CSR matrix, message by message.
+- tests/host/slim_host_plan_main.cpp: slim_host_plan.hpp, i.e. what the SLIM fit decides on the host - where the
+  running vector of the descent lives, the workgroup width, the workgroup count and whether the dynamic-LDS limit is
+  raised, against expectations written out by hand on both sides of every boundary.
 The stream, event and buffer handling of knn.hip itself needs a device and is not compiled here."""
 import os
 import shutil
@@ -235,3 +238,33 @@ def test_sparse_block_plan_plain_optimised_build(tmp_path):
     r = _sparse_block_plan(tmp_path, ["-O3", "-ffp-contract=off"])
     assert r.returncode == 0, r.stderr[-4000:]
     assert "sparse_block_plan ok" in r.stdout
+
+
+def _slim_host_plan(tmp_path, flags):
+    exe = str(tmp_path / "slim_host_plan_main")
+    src = os.path.join(ROOT, "tests", "host", "slim_host_plan_main.cpp")
+    subprocess.check_call([_HOST_CXX, "-std=c++17", "-pthread", *flags, src, "-o", exe])
+    return subprocess.run([exe], capture_output=True, text=True, timeout=600)
+
+
+@pytest.mark.skipif(_HOST_CXX is None, reason="needs a host C++ compiler")
+def test_slim_host_plan_under_address_and_ub_sanitizers(tmp_path):
+    """irspack_amd/csrc/slim_host_plan.hpp - the launch decision of the SLIM descent at 1 item, on both sides of the
+    40 KiB, 64 KiB and 80 KiB steps, at the last catalogue that fits a per-block limit of 64 KiB and of 160 KiB and
+    the first that does not, with the switch off, with fewer and more items than workgroups, and at 2^31 - 1 items
+    (the clamp that keeps the byte count inside an int) - in a program of its own
+    (tests/host/slim_host_plan_main.cpp), every report fatal."""
+    r = _slim_host_plan(tmp_path, ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                                   "-fno-omit-frame-pointer"])
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+    assert "slim_host_plan ok" in r.stdout
+
+
+@pytest.mark.skipif(_HOST_CXX is None, reason="needs a host C++ compiler")
+def test_slim_host_plan_plain_optimised_build(tmp_path):
+    """The same program without a sanitizer at -O3 with the library's -ffp-contract=off: the build whose integer
+    divisions run as the library runs them."""
+    r = _slim_host_plan(tmp_path, ["-O3", "-ffp-contract=off"])
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert "slim_host_plan ok" in r.stdout

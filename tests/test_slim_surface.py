@@ -1,7 +1,9 @@
 """SLIM without a GPU: the Python surface is the reference's (``_util_cpp.pyi:31-48``,
 ``recommenders/slim.py:59-78``), the C ABI declares and exports the calls, the argument checks of
 ``util.hpp:233-236`` come before any device work, and the chunked numpy restatement that arbitrates the
-GPU tests is the plain loop bit for bit."""
+GPU tests is the plain loop bit for bit (also at the chunk widths of the wide workgroups), and embedding a
+matrix into a wider catalogue of items without interactions changes nothing (the lemma
+``tests/test_gpu_slim_wide.py`` rests on)."""
 import inspect
 import os
 import re
@@ -13,7 +15,8 @@ import scipy.sparse as sps
 from _slim_restatement import gram, slim_column, slim_column_plain
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SLIM_SYMBOLS = ["irs_slim_fit", "irs_slim_nnz", "irs_slim_fetch", "irs_slim_last_stats", "irs_slim_destroy"]
+SLIM_SYMBOLS = ["irs_slim_fit", "irs_slim_nnz", "irs_slim_fetch", "irs_slim_last_stats", "irs_slim_last_launch",
+                "irs_slim_destroy"]
 
 
 def _positional(fn):
@@ -122,3 +125,54 @@ def test_chunked_restatement_is_the_plain_loop(positive_only, l2, l1, n_iter, to
             b = slim_column(G, j, l2, l1, n_iter, tol, positive_only, chunk=chunk, dense_fraction=dense_fraction)
             assert a.tobytes() == b.tobytes(), (j, chunk)
         assert np.isfinite(a).all() and a[j] == 0 and a[11] == 0
+
+
+@pytest.mark.parametrize("positive_only", [True, False])
+@pytest.mark.parametrize("l2, l1, n_iter, tol", [(5.0, 0.5, 4, 0.0), (0.0, 0.0, 3, 0.0), (2.0, 1.0, 6, 1e-3)])
+def test_chunked_restatement_is_the_plain_loop_at_the_wide_chunks(positive_only, l2, l1, n_iter, tol):
+    """The chunk widths of the device's three workgroup sizes (and 64, one wave) on a problem of several
+    chunks of each: 1,340 coordinates, so the last chunk is partial at every width; target columns at the
+    seams of the 512- and 1024-wide chunks, at both ends and on the item without interactions.
+    ``dense_fraction = 2.0``: never the plain sweep inside ``slim_column``."""
+    rng = np.random.default_rng(7)
+    X = (rng.random((300, 1340)) < 0.04) * rng.integers(1, 6, size=(300, 1340))
+    X[:, 777] = 0  # an item without interactions: G_ff + l2 == 0 when l2 == 0
+    G = gram(X)
+    for j in (0, 511, 512, 777, 1023, 1024, 1339):
+        a = slim_column_plain(G, j, l2, l1, n_iter, tol, positive_only)
+        for chunk in (64, 256, 512, 1024):
+            b = slim_column(G, j, l2, l1, n_iter, tol, positive_only, chunk=chunk, dense_fraction=2.0)
+            assert a.tobytes() == b.tobytes(), (j, chunk)
+        assert np.isfinite(a).all() and a[j] == 0 and a[777] == 0
+        assert a.any() or j == 777, j
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("positive_only", [True, False])
+@pytest.mark.parametrize("l2, l1", [(5.0, 0.5), (5.0, 0.0), (0.0, 0.5), (0.0, 0.0)])
+def test_embedding_into_a_wider_catalogue_changes_nothing(dtype, positive_only, l2, l1):
+    """Embedding lemma (tests/test_gpu_slim_wide.py rests on it): a matrix embedded into a wider one whose
+    extra items have no interactions - every touched column keeps its coefficients bit for bit at the
+    touched coordinates, every other coefficient is zero, a column of an extra item is all zero.  An extra
+    coordinate f has G[f, :] = 0: its candidate is (-0 -+ l1) / (0 + l2), never > 0 as plus and never < 0 as
+    minus (0 / 0 and -l1 / 0 fail both tests), so it never changes and never enters the running product; the
+    touched coordinates then see the operations of the small problem in the same order.  400 touched of
+    1,500 items, 3 sweeps (unconverged)."""
+    n_small, n_big, n_iter = 400, 1500, 3
+    rng = np.random.default_rng(11)
+    small = (rng.random((200, n_small)) < 0.06) * rng.integers(1, 6, size=(200, n_small))
+    assert (small != 0).sum(axis=0).min() > 0
+    touched = np.sort(rng.choice(n_big, size=n_small, replace=False))
+    extra = np.setdiff1d(np.arange(n_big), touched)
+    big = np.zeros((200, n_big), dtype=small.dtype)
+    big[:, touched] = small
+    G_small, G_big = gram(small, dtype), gram(big, dtype)
+    assert G_big.dtype == dtype and not G_big[extra].any() and not G_big[:, extra].any()
+    for c in (0, 1, 199, 398, 399):
+        w_small = slim_column(G_small, c, l2, l1, n_iter, 0.0, positive_only)
+        w_big = slim_column(G_big, int(touched[c]), l2, l1, n_iter, 0.0, positive_only, chunk=1024)
+        assert w_small.dtype == dtype and w_small.any()
+        assert w_big[touched].tobytes() == w_small.tobytes(), c
+        assert not w_big[extra].any(), c
+    for j in (int(extra[0]), int(extra[-1])):
+        assert not slim_column(G_big, j, l2, l1, n_iter, 0.0, positive_only, chunk=1024).any(), j
