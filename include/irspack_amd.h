@@ -582,6 +582,49 @@ irs_status irs_slim_last_launch(irs_slim_result *r, int32_t *lds_r, int32_t *lds
                                 int32_t *n_wg, int32_t *raise_dynamic_lds, int64_t *lds_per_block);
 irs_status irs_slim_destroy(irs_slim_result *r);
 
+/* ------------------------------------------------------------------ row-wise hold-out split
+ * rowwise_train_test_split_by_ratio / _by_fixed_n of irspack.utils._util_cpp (SplitFunction,
+ * cpp_source/util.hpp:72-156): every row of X is split into a train and a test (held-out) part, on the device.
+ * The reference's result depends on libstdc++'s std::shuffle; this library has a rule of its own (normative text:
+ * irspack_amd/csrc/split_host_plan.hpp), a function of the arguments alone:
+ *   every stored entry takes part (explicit zeros too); j = position of an entry in its row, m = the row's length;
+ *   n_test(m) = floor or ceil of double(m) * heldout_ratio, computed in double (mode IRS_SPLIT_BY_RATIO), or
+ *               min(m, n_held_out) (mode IRS_SPLIT_BY_FIXED_N) - util.hpp:127-150;
+ *   row_key = mix64(mix64(seed) ^ mix64(row + 0x53504C4954)), key(j) = mix64(row_key ^ mix64(j)), mix64 being the
+ *   finaliser of splitmix64; held out are the n_test smallest pairs (key(j), j) of the row.
+ * X is CSR [rows, cols]: indptr int64, indices int32, data opaque elements of elem_bytes = 1, 2, 4 or 8 bytes, which
+ * are moved and never converted.  Validated on the host before any device work (IRS_INVALID_ARGUMENT): monotone
+ * indptr, column indices in range and strictly ascending within a row (duplicates are not summed), the element
+ * width, 0 <= heldout_ratio <= 1 (the reference's message), n_held_out >= 0, the mode.  Zero rows or zero stored
+ * entries succeed with empty outputs and without a device.
+ * Both results have X's shape and keep the column order inside a row; the handle holds them on the host.  The fetch
+ * arrays are caller-owned: indptr int64[rows + 1], indices int32[nnz], data elem_bytes * nnz bytes each (sizes from
+ * the nnz call; the pointers of a matrix without entries may be NULL). */
+#define IRS_SPLIT_BY_RATIO 0
+#define IRS_SPLIT_BY_FIXED_N 1
+typedef struct irs_split_result irs_split_result;
+typedef struct {
+  double upload_ms;    /* HIP events: the matrix and the row lists to the device */
+  double select_ms;    /* the threshold key of every row with 0 < n_test < m */
+  double scan_ms;      /* the two row-pointer arrays */
+  double scatter_ms;   /* flags and the ordered compaction into both outputs */
+  double d2h_ms;       /* the copy back into the handle */
+  int64_t rows_empty;  /* rows per class: no entries, */
+  int64_t rows_wave;   /* 1 .. 64 entries (a wave per row), */
+  int64_t rows_lds;    /* 65 .. 4096 (a workgroup per row, keys in LDS), */
+  int64_t rows_stream; /* longer (a workgroup per row, keys recomputed per pass) */
+} irs_split_stats;
+irs_status irs_split_rowwise(int64_t rows, int64_t cols, const int64_t *indptr, const int32_t *indices,
+                             const void *data, int32_t elem_bytes, int64_t random_seed, int32_t mode,
+                             double heldout_ratio, int32_t n_test_ceil, int64_t n_held_out, int32_t device,
+                             irs_split_result **out);
+irs_status irs_split_nnz(irs_split_result *r, int64_t *nnz_train, int64_t *nnz_test);
+irs_status irs_split_fetch(irs_split_result *r, int64_t *train_indptr, int32_t *train_indices, void *train_data,
+                           int64_t *test_indptr, int32_t *test_indices, void *test_data);
+/* Measurement only: the phase times and the rows per class of the call that produced the result. */
+irs_status irs_split_last_stats(irs_split_result *r, irs_split_stats *stats);
+irs_status irs_split_destroy(irs_split_result *r);
+
 /* ------------------------------------------------------------------ EASE / EDLAE
  * DenseSLIMRecommender (src/irspack/recommenders/dense_slim.py:39-53) and EDLAERecommender
  * (edlae.py:49-66): the closed-form item-item weights, float32 throughout, on the device:

@@ -8,3 +8,13 @@ fallback: compute entry points raise when no HIP device is visible.
 """
 
 __version__ = "0.1.0"
+
+_LAZY = ("rowwise_train_test_split", "df_to_sparse")  # of irspack_amd.utils, imported on first use
+
+
+def __getattr__(name):
+    if name in _LAZY:
+        from . import utils
+
+        return getattr(utils, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

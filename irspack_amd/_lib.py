@@ -180,6 +180,22 @@ class MultVaeStatsStruct(C.Structure):  # irs_multvae_stats_t
     ]
 
 
+class SplitStatsStruct(C.Structure):  # irs_split_stats
+    _fields_ = [
+        ("upload_ms", C.c_double),
+        ("select_ms", C.c_double),
+        ("scan_ms", C.c_double),
+        ("scatter_ms", C.c_double),
+        ("d2h_ms", C.c_double),
+        ("rows_empty", C.c_int64),
+        ("rows_wave", C.c_int64),
+        ("rows_lds", C.c_int64),
+        ("rows_stream", C.c_int64),
+    ]
+
+
+SPLIT_BY_RATIO, SPLIT_BY_FIXED_N = 0, 1  # IRS_SPLIT_BY_* of include/irspack_amd.h
+
 ABI_VERSION = 4  # IRS_ABI_VERSION of include/irspack_amd.h
 # IRS_EXCHANGE_* of include/irspack_amd.h: how irs_ials_sharded_step moves the solved rows
 EXCHANGE_MODES = {"auto": 0, "broadcast": 1, "mesh": 2, "peer": 3}
@@ -244,6 +260,11 @@ EXPORTED_SYMBOLS = [
     "irs_slim_last_stats",
     "irs_slim_last_launch",
     "irs_slim_destroy",
+    "irs_split_rowwise",
+    "irs_split_nnz",
+    "irs_split_fetch",
+    "irs_split_last_stats",
+    "irs_split_destroy",
     "irs_dense_slim_fit",
     "irs_truncsvd_create",
     "irs_truncsvd_range",
@@ -319,6 +340,13 @@ ARGTYPES = {
     "irs_slim_last_launch": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)],
     "irs_slim_destroy": [C.c_void_p],
+    "irs_split_rowwise": [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_void_p, C.c_int32,
+                          C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)],
+    "irs_split_nnz": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "irs_split_fetch": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int64),
+                        C.POINTER(C.c_int32), C.c_void_p],
+    "irs_split_last_stats": [C.c_void_p, C.c_void_p],
+    "irs_split_destroy": [C.c_void_p],
     "irs_dense_slim_fit": [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float),
                            C.c_float, C.c_float, C.c_int32, C.POINTER(C.c_float), C.c_void_p],
     "irs_truncsvd_create": [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float),

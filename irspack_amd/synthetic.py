@@ -124,7 +124,8 @@ def describe(X: sps.csr_matrix) -> Dict[str, float]:
 
 def holdout_split(X: sps.csr_matrix, ratio: float = 0.2, seed: int = 7
                   ) -> Tuple[sps.csr_matrix, sps.csr_matrix]:
-    """Per-row random hold-out (own splitter; the reference's split/ is out of scope)."""
+    """Per-entry random hold-out with numpy's generator on the host (what the benchmarks and tests have always
+    used; the device split is ``irspack_amd.utils.rowwise_train_test_split``)."""
     X = X.tocsr()
     rng = np.random.default_rng(seed)
     keep = rng.random(X.nnz) >= ratio

@@ -4,7 +4,7 @@
 reference computes with scipy inside ``recommenders/dense_slim.py`` and ``recommenders/edlae.py``; and the
 randomized truncated SVD (``truncated_svd``), which the reference takes from scikit-learn inside
 ``recommenders/truncsvd.py``; and the coordinate-descent NMF (``nmf_fit``, ``nmf_transform``), which the reference takes
-from scikit-learn inside ``recommenders/nmf.py``.
+from scikit-learn inside ``recommenders/nmf.py``; and the row-wise hold-out split (util.hpp:72-156, ``_split.py``).
 
 Everything goes through the C ABI: ``remove_diagonal``, the serving top-k
 ``retrieve_recommend_from_score`` and the two feature weightings (``irs_knn_weight``; the kNN
@@ -573,3 +573,6 @@ def nmf_transform(X, H: np.ndarray, alpha: float = 0.0, l1_ratio: float = 0.0, *
 
 # irspack/utils/__init__.py exports the ID mappers from here (they import retrieve_recommend_from_score above)
 from .id_mapping import IDMapper, ItemIDMapper  # noqa: E402,F401
+# the row-wise hold-out split (util.hpp:72-156) with convert_randomstate and df_to_sparse
+from ._split import (convert_randomstate, df_to_sparse, rowwise_train_test_split,  # noqa: E402,F401
+                     rowwise_train_test_split_by_fixed_n, rowwise_train_test_split_by_ratio)
