@@ -1,13 +1,17 @@
 """Minimal recommender base: the caller contract of the reference's
 ``irspack/recommenders/base.py:79-126, 290-337, 406-429`` that the hot path relies on
-(matrix normalisation, ``learn``, seen-item masking, similarity scoring).  Tuning,
-the registry metaclass and config classes are orchestration and out of scope.
+(matrix normalisation, ``learn``, seen-item masking, similarity scoring), and its tuning entry
+points (``base.py:132-282``: ``default_tune_range``, ``learn_with_optimizer``, ``tune``) on top of
+``irspack_amd.optimization``.  The registry metaclass and config classes are out of scope.
 """
 
-from typing import Any, Callable, Optional, Union
+import logging
+from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
 import numpy as np
 import scipy.sparse as sps
+
+from ..optimization.parameter_range import ParameterRange
 
 
 def _sparse_to_array(U: Any) -> np.ndarray:
@@ -17,16 +21,72 @@ def _sparse_to_array(U: Any) -> np.ndarray:
 
 
 class BaseRecommender:
+    # the ranges that ``tune`` searches when the caller gives no ``parameter_suggest_function``
+    default_tune_range: List[ParameterRange] = []
+
     def __init__(self, X_train_all: Any, **kwargs: Any) -> None:
         # base.py:94-101
         self.X_train_all: sps.csr_matrix = sps.csr_matrix(X_train_all).astype(np.float64)
         self.n_users: int = self.X_train_all.shape[0]
         self.n_items: int = self.X_train_all.shape[1]
         self.X_train_all.sort_indices()
+        # what the fit itself settles, e.g. the epoch with the best validation score (base.py:103-105)
+        self.learnt_config: Dict[str, Any] = {}
 
     def learn(self):
         self._learn()
         return self
+
+    def learn_with_optimizer(self, evaluator: Any, trial: Any, max_epoch: int = 128, validate_epoch: int = 5,
+                             score_degradation_max: int = 5) -> None:
+        """base.py:132-163: the fit of one tuning trial.  A class that does not train by epochs has nothing to
+        stop early or prune, so the evaluator, the trial and the three numbers play no part."""
+        self.learn()
+
+    @classmethod
+    def default_suggest_parameter(cls, trial: Any, recommender_params: Dict[str, Any]) -> Dict[str, Any]:
+        # base.py:165-173: a fixed parameter is not searched
+        return {r.name: r.suggest(trial) for r in cls.default_tune_range if r.name not in recommender_params}
+
+    @classmethod
+    def tune(cls, data: Any, evaluator: Any, study: Any = None, n_trials: int = 20,
+             timeout: Optional[int] = None, data_suggest_function: Optional[Callable[[Any], Any]] = None,
+             parameter_suggest_function: Optional[Callable[[Any], Dict[str, Any]]] = None,
+             tuning_random_seed: Optional[int] = None, prunning_n_startup_trials: int = 10, max_epoch: int = 128,
+             validate_epoch: int = 5, score_degradation_max: int = 5, logger: Optional[logging.Logger] = None,
+             **recommender_params: Any) -> Tuple[Dict[str, Any], Any]:
+        """base.py:176-282: searches the constructor arguments of ``cls`` for the best score of ``evaluator``.
+
+        ``data`` is the training matrix; a ``data_suggest_function(trial)`` can give one per trial instead, with
+        ``data=None``.  ``parameter_suggest_function(trial)`` replaces ``default_tune_range`` as the source of the
+        searched arguments.  ``recommender_params`` are fixed arguments of every trial's constructor: they win over
+        a suggested argument of the same name and are not part of the returned parameters.  ``study`` may be a
+        study of ``irspack_amd.optimization`` or an ``optuna.Study``; ``None`` creates an in-memory study with
+        ``TPESampler(seed=tuning_random_seed)`` and ``MedianPruner(n_startup_trials=prunning_n_startup_trials)``.
+        ``n_trials`` counts pruned trials too, ``timeout`` (seconds) is looked at between trials, and
+        ``max_epoch``, ``validate_epoch`` and ``score_degradation_max`` go to ``learn_with_optimizer``.
+
+        Returns the best trial's parameters (searched and learnt, such as ``train_epochs``) and a pandas frame
+        with one row per trial."""
+        from ..optimization.optimizer import Optimizer
+
+        if study is None:
+            from ..optimization.study import MedianPruner, TPESampler, create_study
+
+            study = create_study(sampler=TPESampler(seed=tuning_random_seed),
+                                 pruner=MedianPruner(n_startup_trials=prunning_n_startup_trials))
+        if data is None and data_suggest_function is None:
+            raise ValueError("Either `data` or `data_suggest_function` must be provided.")
+        if data is not None:
+            def data_suggest_function(trial: Any) -> Any:
+                return data
+        if parameter_suggest_function is None:
+            def parameter_suggest_function(trial: Any) -> Dict[str, Any]:
+                return cls.default_suggest_parameter(trial, recommender_params)
+        optimizer = Optimizer(data_suggest_function, parameter_suggest_function, recommender_params, evaluator,
+                              logger=logger, max_epoch=max_epoch, validate_epoch=validate_epoch,
+                              score_degradation_max=score_degradation_max)
+        return optimizer.optimize_with_study(study, cls, n_trials=n_trials, timeout=timeout)
 
     def _learn(self) -> None:
         raise NotImplementedError("_learn must be implemented.")

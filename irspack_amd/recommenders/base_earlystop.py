@@ -1,6 +1,6 @@
 """``BaseRecommenderWithEarlyStopping`` (irspack/recommenders/base_earlystop.py:52-149): recommenders that are
-fitted epoch by epoch by a trainer object and can stop against a validation evaluator.  The Optuna and
-progress-bar parts of the reference's loop are orchestration and left out."""
+fitted epoch by epoch by a trainer object and can stop against a validation evaluator, reporting to a tuning
+trial that may prune the fit.  The progress bar of the reference's loop is left out."""
 
 from io import BytesIO
 from typing import IO, Any, Optional
@@ -27,7 +27,6 @@ class BaseRecommenderWithEarlyStopping(BaseRecommender):
         self.train_epochs = train_epochs
         self.trainer: Optional[Any] = None
         self.best_state: Optional[bytes] = None
-        self.learnt_config = {}
 
     def _create_trainer(self) -> Any:
         raise NotImplementedError("_create_trainer must be implemented.")
@@ -61,10 +60,18 @@ class BaseRecommenderWithEarlyStopping(BaseRecommender):
 
     def learn_with_evaluator(self, evaluator: Any, max_epoch: int = 128, validate_epoch: int = 5,
                              score_degradation_max: int = 5) -> None:
-        """base_earlystop.py:106-149 without the progress bar / Optuna hooks: every
-        ``validate_epoch`` epochs the evaluator scores the model; the best state is kept and
-        restored at the end, and ``score_degradation_max`` validations in a row without a new best
-        end the fit.  ``evaluator=None``: exactly ``max_epoch`` epochs."""
+        """base_earlystop.py:106-149 without a trial: every ``validate_epoch`` epochs the evaluator
+        scores the model; the best state is kept and restored at the end, and
+        ``score_degradation_max`` validations in a row without a new best end the fit.
+        ``evaluator=None``: exactly ``max_epoch`` epochs."""
+        self.learn_with_optimizer(evaluator, None, max_epoch=max_epoch, validate_epoch=validate_epoch,
+                                  score_degradation_max=score_degradation_max)
+
+    def learn_with_optimizer(self, evaluator: Any, trial: Any, max_epoch: int = 128, validate_epoch: int = 5,
+                             score_degradation_max: int = 5) -> None:
+        """base_earlystop.py:106-149: the loop of ``learn_with_evaluator``; after every validation that did not
+        end the fit, ``trial`` (if any) is told minus the score at the 0-based epoch and asked whether to go on:
+        ``TrialPruned`` is raised if not."""
         self.start_learning()
         best, misses = -float("inf"), 0
         for done in range(1, max_epoch + 1):
@@ -76,9 +83,15 @@ class BaseRecommenderWithEarlyStopping(BaseRecommender):
                 best, misses = score, 0
                 self.save_state()
                 self.learnt_config["train_epochs"] = done
-                continue
-            misses += 1
-            if misses >= score_degradation_max:
-                break
+            else:
+                misses += 1
+                if misses >= score_degradation_max:
+                    break
+            if trial is not None:
+                trial.report(-score, done - 1)
+                if trial.should_prune():
+                    from ..optimization.study import TrialPruned
+
+                    raise TrialPruned()
         if evaluator is not None and self.best_state is not None:
             self.load_state()

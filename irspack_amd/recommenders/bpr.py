@@ -12,6 +12,7 @@ import numpy as np
 from .. import _lib
 from .._lib import check, lib, ptr
 from .._threading import get_n_threads
+from ..optimization.parameter_range import LogUniformFloatRange, UniformIntegerRange
 from .base_earlystop import BaseRecommenderWithEarlyStopping, TrainerBase
 
 _TABLES = ("U", "V", "b", "GU", "GV", "Gb")
@@ -176,6 +177,11 @@ class BPRFMTrainer(TrainerBase):
 class BPRFMRecommender(BaseRecommenderWithEarlyStopping):
     """bpr.py:60-184: the reference's arguments in the reference's order; ``learning_rate``, ``batch_size``,
     ``random_seed`` and ``device`` are keyword extensions.  ``item_biases`` replaces ``fm.item_biases``."""
+
+    # (bpr.py:100-105 without CategoricalRange("loss", ...): loss="warp" is WARPFMRecommender here, which inherits
+    # the three ranges)
+    default_tune_range = [UniformIntegerRange("n_components", 4, 256), LogUniformFloatRange("item_alpha", 1e-9, 1e-2),
+                          LogUniformFloatRange("user_alpha", 1e-9, 1e-2)]
 
     def __init__(self, X_train_all: Any, n_components: int = 128, item_alpha: float = 1e-9, user_alpha: float = 1e-9,
                  loss: str = "bpr", n_threads: Optional[int] = None, train_epochs: int = 128, *,

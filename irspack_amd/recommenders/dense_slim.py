@@ -3,6 +3,7 @@ weights, computed on the device by ``irspack_amd.utils.dense_slim_weight`` (``ir
 
 from typing import Any
 
+from ..optimization.parameter_range import LogUniformFloatRange
 from ..utils import dense_slim_weight
 from .base import BaseSimilarityRecommender
 
@@ -18,6 +19,8 @@ class DenseSLIMRecommender(BaseSimilarityRecommender):
     in float32.  ``W`` is a dense float32 ``ndarray``.  The inverse comes from a Cholesky factor, so a
     system that is not positive definite (``reg <= 0`` with an item nobody touched) raises
     ``numpy.linalg.LinAlgError``."""
+
+    default_tune_range = [LogUniformFloatRange("reg", 1, 1e4)]
 
     def __init__(self, X_train_all: Any, reg: float = 1) -> None:
         super().__init__(X_train_all)

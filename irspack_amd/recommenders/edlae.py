@@ -5,6 +5,7 @@ from typing import Any
 
 import numpy as np
 
+from ..optimization.parameter_range import LogUniformFloatRange, UniformFloatRange
 from ..utils import dense_slim_weight
 from .base import BaseSimilarityRecommender
 
@@ -21,6 +22,8 @@ class EDLAERecommender(BaseSimilarityRecommender):
     on the diagonal, ``p = dropout_p``.  ``dropout_p == 1`` raises ``ZeroDivisionError`` (the expression
     is the reference's).  Unlike the reference's LU inverse, ``dropout_p > 1`` (an indefinite system) raises
     ``numpy.linalg.LinAlgError``: the inverse comes from a Cholesky factor."""
+
+    default_tune_range = [LogUniformFloatRange("reg", 1, 1e4), UniformFloatRange("dropout_p", 0.0, 0.99)]
 
     def __init__(self, X_train_all: Any, reg: float = 1.0, dropout_p: float = 0.1) -> None:
         super().__init__(X_train_all)

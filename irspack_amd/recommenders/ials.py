@@ -5,17 +5,19 @@ Reproduces what the reference's Python does around the native calls: float32 cas
 (:91), log confidence scaling (:437-446), the ``nu_star`` regulariser rescale
 (:232-242, 412-418), the two solver configs (training / prediction time), the
 epoch loop, scoring and fold-in.  Early stopping against a validation evaluator
-follows ``base_earlystop.py:106-149`` without the Optuna / progress-bar parts.
+follows ``base_earlystop.py:106-149`` without the progress bar.
 """
 
 import enum
+import logging
 import pickle
-from typing import IO, Any, Callable, Optional
+from typing import IO, Any, Callable, Dict, Optional, Tuple
 
 import numpy as np
 import scipy.sparse as sps
 
 from .._threading import get_n_threads
+from ..optimization.parameter_range import LogUniformFloatRange, UniformIntegerRange
 from ._ials_core import IALSModelConfigBuilder, IALSSolverConfigBuilder
 from ._ials_core import IALSTrainer as CoreTrainer
 from ._ials_core import LossType, SolverType
@@ -148,6 +150,9 @@ class IALSRecommender(BaseRecommenderWithEarlyStopping):
     """ials.py:245-562.  Same constructor arguments and defaults; ``device`` is an extra
     keyword.  ``user_features`` / ``item_features`` (dense or CSR, one row per user / item)
     switch on the feature-aware model (trainer hpp:722-789)."""
+
+    default_tune_range = [UniformIntegerRange("n_components", 4, 300), LogUniformFloatRange("alpha0", 3e-3, 1),
+                          LogUniformFloatRange("reg", 1e-4, 1e-1)]
 
     def __init__(self, X_train_all: Any, n_components: int = 20, alpha0: float = 0.0,
                  reg: float = 1e-3, nu: float = 1.0, confidence_scaling: str = "none",
@@ -306,3 +311,84 @@ class IALSRecommender(BaseRecommenderWithEarlyStopping):
         # ials.py:624-628
         return self.get_score_from_item_embedding(
             user_indices, self.compute_item_embedding_from_features(item_features))
+
+    # -- tuning (ials.py:637-791) ----------------------------------------------
+    @classmethod
+    def tune(cls, data: Any, evaluator: Any, study: Any = None, n_trials: int = 20, timeout: Optional[int] = None,
+             data_suggest_function: Optional[Callable[[Any], Any]] = None,
+             parameter_suggest_function: Optional[Callable[[Any], Dict[str, Any]]] = None,
+             tuning_random_seed: Optional[int] = None, prunning_n_startup_trials: int = 10, max_epoch: int = 16,
+             validate_epoch: int = 1, score_degradation_max: int = 3, logger: Optional[logging.Logger] = None,
+             **recommender_params: Any) -> Tuple[Dict[str, Any], Any]:
+        """``BaseRecommender.tune`` with iALS's own defaults (ials.py:758-791): at most 16 epochs, validated after
+        every one, given up after 3 validations in a row without a new best."""
+        return super().tune(data=data, evaluator=evaluator, study=study, n_trials=n_trials, timeout=timeout,
+                            data_suggest_function=data_suggest_function,
+                            parameter_suggest_function=parameter_suggest_function,
+                            tuning_random_seed=tuning_random_seed,
+                            prunning_n_startup_trials=prunning_n_startup_trials, max_epoch=max_epoch,
+                            validate_epoch=validate_epoch, score_degradation_max=score_degradation_max,
+                            logger=logger, **recommender_params)
+
+    @classmethod
+    def tune_doubling_dimension(cls, data: Any, evaluator: Any, initial_dimension: int, maximal_dimension: int,
+                                storage: Any = None, study_name_prefix: Optional[str] = None,
+                                n_trials_initial: int = 40, n_trials_following: int = 20,
+                                n_startup_trials_initial: int = 10, n_startup_trials_following: int = 5,
+                                max_epoch: int = 16, validate_epoch: int = 1, score_degradation_max: int = 3,
+                                neighborhood_scale: float = 3.0,
+                                suggest_function_initial: Optional[Callable[[Any], Dict[str, Any]]] = None,
+                                random_seed: Optional[int] = None) -> Tuple[Dict[str, Any], Any]:
+        """ials.py:637-756, the tuning strategy of `Revisiting the Performance of iALS on Item Recommendation
+        Benchmarks <https://arxiv.org/abs/2110.14037>`_: one study per ``n_components`` in ``initial_dimension``,
+        twice that, ... up to ``maximal_dimension`` (inclusive).  The first study searches widely
+        (``n_trials_initial`` trials over ``default_tune_range`` or ``suggest_function_initial``); each later one
+        runs ``n_trials_following`` trials and searches only the float-valued best parameters of the study before
+        it, log-uniformly within a factor ``neighborhood_scale`` either way.  ``n_startup_trials_*`` go to the
+        studies' ``MedianPruner``; ``random_seed``, if given, is incremented before each study and seeds its
+        ``TPESampler``.  Study ``d`` is named ``"<study_name_prefix>_<d>"``.  The studies are in-memory ones of
+        ``irspack_amd.optimization``, which has no storage back end: ``storage`` must be ``None``.
+
+        Returns the best parameters over all dimensions (with ``n_components``) and the studies' frames one below
+        the other, with an ``n_components`` column."""
+        import pandas as pd
+
+        from ..optimization.study import MedianPruner, TPESampler, create_study
+
+        if storage is not None:
+            raise ValueError("the built-in study keeps its trials in memory: `storage` must be None.")
+        if study_name_prefix is None:
+            from uuid import uuid1
+
+            study_name_prefix = str(uuid1())
+        results = []  # (best value, best parameters, frame) per dimension
+        previous_best: Optional[Dict[str, Any]] = None
+        dimension = initial_dimension
+        while dimension <= maximal_dimension:
+            if random_seed is not None:
+                random_seed += 1
+            if previous_best is None:
+                suggest = suggest_function_initial
+                n_trials, n_startup_trials = n_trials_initial, n_startup_trials_initial
+            else:
+                n_trials, n_startup_trials = n_trials_following, n_startup_trials_following
+
+                def suggest(trial: Any, centre: Dict[str, Any] = dict(previous_best)) -> Dict[str, Any]:
+                    return {name: trial.suggest_float(name, value / neighborhood_scale, value * neighborhood_scale,
+                                                      log=True)
+                            for name, value in centre.items() if isinstance(value, float)}
+
+            study = create_study(sampler=TPESampler(seed=random_seed),
+                                 pruner=MedianPruner(n_startup_trials=n_startup_trials),
+                                 study_name=f"{study_name_prefix}_{dimension}")
+            best_params, frame = cls.tune(data, evaluator, study=study, n_trials=n_trials, max_epoch=max_epoch,
+                                          validate_epoch=validate_epoch, score_degradation_max=score_degradation_max,
+                                          parameter_suggest_function=suggest, n_components=dimension)
+            frame["n_components"] = dimension
+            best_params["n_components"] = dimension
+            results.append((float(frame["value"].min()), best_params, frame))
+            previous_best = dict(study.best_params)
+            dimension *= 2
+        if not results:
+            raise ValueError("initial_dimension is larger than maximal_dimension: nothing to tune.")
+        return min(results, key=lambda r: r[0])[1], pd.concat([r[2] for r in results])

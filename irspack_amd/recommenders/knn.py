@@ -12,6 +12,9 @@ import enum
 from typing import Any, Optional
 
 from .._threading import get_n_threads
+from ..optimization.parameter_range import (CategoricalRange, LogUniformFloatRange, UniformFloatRange,
+                                            UniformIntegerRange, default_tune_range_knn,
+                                            default_tune_range_knn_with_weighting)
 from ._knn import (AsymmetricSimilarityComputer, CosineSimilarityComputer,
                    JaccardSimilarityComputer, P3alphaComputer, RP3betaComputer,
                    TverskyIndexComputer)
@@ -25,6 +28,8 @@ class FeatureWeightingScheme(str, enum.Enum):
 
 
 class BaseKNNRecommender(BaseSimilarityRecommender):
+    default_tune_range = default_tune_range_knn
+
     def __init__(self, X_train_all: Any, shrinkage: float = 0.0, top_k: int = 100,
                  n_threads: Optional[int] = None, feature_weighting: str = "NONE",
                  bm25_k1: float = 1.2, bm25_b: float = 0.75) -> None:
@@ -62,6 +67,8 @@ class BaseKNNRecommender(BaseSimilarityRecommender):
 
 
 class CosineKNNRecommender(BaseKNNRecommender):  # knn.py:94-161
+    default_tune_range = default_tune_range_knn_with_weighting + [CategoricalRange("normalize", [False, True])]
+
     def __init__(self, X_train_all: Any, shrinkage: float = 0.0, normalize: bool = False,
                  top_k: int = 100, feature_weighting: str = "NONE", bm25_k1: float = 1.2,
                  bm25_b: float = 0.75, n_threads: Optional[int] = None) -> None:
@@ -73,6 +80,8 @@ class CosineKNNRecommender(BaseKNNRecommender):  # knn.py:94-161
 
 
 class AsymmetricCosineKNNRecommender(BaseKNNRecommender):  # knn.py:168-235
+    default_tune_range = default_tune_range_knn_with_weighting + [UniformFloatRange("alpha", 0, 1)]
+
     def __init__(self, X_train_all: Any, shrinkage: float = 0.0, alpha: float = 0.5,
                  top_k: int = 100, feature_weighting: str = "NONE", bm25_k1: float = 1.2,
                  bm25_b: float = 0.75, n_threads: Optional[int] = None) -> None:
@@ -84,6 +93,8 @@ class AsymmetricCosineKNNRecommender(BaseKNNRecommender):  # knn.py:168-235
 
 
 class JaccardKNNRecommender(BaseKNNRecommender):  # knn.py:238-270
+    default_tune_range = list(default_tune_range_knn)
+
     def __init__(self, X_train_all: Any, shrinkage: float = 0.0, top_k: int = 100,
                  n_threads: Optional[int] = None) -> None:
         super().__init__(X_train_all, shrinkage, top_k, n_threads)
@@ -93,6 +104,8 @@ class JaccardKNNRecommender(BaseKNNRecommender):  # knn.py:238-270
 
 
 class TverskyIndexKNNRecommender(BaseKNNRecommender):  # knn.py:273-326
+    default_tune_range = default_tune_range_knn + [UniformFloatRange("alpha", 0, 2), UniformFloatRange("beta", 0, 2)]
+
     def __init__(self, X_train_all: Any, shrinkage: float = 0.0, alpha: float = 0.5,
                  beta: float = 0.5, top_k: int = 100, n_threads: Optional[int] = None) -> None:
         super().__init__(X_train_all, shrinkage, top_k, n_threads)
@@ -104,6 +117,9 @@ class TverskyIndexKNNRecommender(BaseKNNRecommender):  # knn.py:273-326
 
 
 class P3alphaRecommender(BaseSimilarityRecommender):  # p3.py:44-76
+    default_tune_range = [UniformIntegerRange("top_k", low=10, high=1000),
+                          CategoricalRange("normalize_weight", [True, False])]
+
     def __init__(self, X_train_all: Any, alpha: float = 1, top_k: Optional[int] = None,
                  normalize_weight: bool = False, n_threads: Optional[int] = None) -> None:
         super().__init__(X_train_all)
@@ -128,6 +144,9 @@ class P3alphaRecommender(BaseSimilarityRecommender):  # p3.py:44-76
 
 
 class RP3betaRecommender(BaseSimilarityRecommender):  # rp3.py:49-84
+    default_tune_range = [UniformIntegerRange("top_k", 2, 1000), LogUniformFloatRange("beta", 1e-5, 5e-1),
+                          CategoricalRange("normalize_weight", [True, False])]
+
     def __init__(self, X_train_all: Any, alpha: float = 1, beta: float = 0.6,
                  top_k: Optional[int] = None, normalize_weight: bool = False,
                  n_threads: Optional[int] = None) -> None:

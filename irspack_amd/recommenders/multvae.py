@@ -12,6 +12,7 @@ import scipy.sparse as sps
 
 from .. import _lib
 from .._lib import check, lib, ptr, ptr_array
+from ..optimization.parameter_range import CategoricalRange
 from .base_earlystop import BaseRecommenderWithEarlyStopping, TrainerBase
 
 TABLES = ("W1", "b1", "W2", "b2", "W3", "b3", "W4", "b4")
@@ -208,6 +209,10 @@ class MultVAERecommender(BaseRecommenderWithEarlyStopping):
 
     ``l2_regularizer`` is accepted and stored and has no effect, as in the reference (its loss never reads it).
     ``enc_hidden_dims`` and ``dec_hidden_dims`` are at most 574."""
+
+    default_tune_range = [CategoricalRange("dim_z", [32, 64, 128, 256]),
+                          CategoricalRange("enc_hidden_dims", [128, 256, 512]),
+                          CategoricalRange("kl_anneal_goal", [0.1, 0.2, 0.4])]
 
     def __init__(self, X_train_all: Any, dim_z: int = 16, enc_hidden_dims: int = 256,
                  dec_hidden_dims: Optional[int] = None, dropout_p: float = 0.5, l2_regularizer: float = 0,

@@ -7,6 +7,7 @@ from typing import Any, Optional
 
 import numpy as np
 
+from ..optimization.parameter_range import LogUniformFloatRange, UniformFloatRange, UniformIntegerRange
 from ..utils import NMF_INITS, nmf_fit, nmf_transform
 from .base import BaseRecommender
 
@@ -27,6 +28,9 @@ class NMFModel:
 
 
 class NMFRecommender(BaseRecommender):
+    default_tune_range = [UniformIntegerRange("n_components", 4, 512), LogUniformFloatRange("alpha", 1e-10, 1e-1),
+                          UniformFloatRange("l1_ratio", 0, 1)]
+
     def __init__(self, X_train_all: Any, n_components: int = 64, alpha: float = 1e-2, l1_ratio: float = 1e-2,
                  beta_loss: str = "frobenius", init: Optional[str] = None) -> None:
         super().__init__(X_train_all)

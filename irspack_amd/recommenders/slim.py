@@ -4,6 +4,7 @@ device by ``irspack_amd.utils.slim_weight_*`` (``irs_slim_fit``)."""
 from typing import Any, Optional
 
 from .._threading import get_n_threads
+from ..optimization.parameter_range import LogUniformFloatRange, UniformFloatRange
 from ..utils import slim_weight_allow_negative, slim_weight_positive_only
 from .base import BaseSimilarityRecommender
 
@@ -19,6 +20,8 @@ class SLIMRecommender(BaseSimilarityRecommender):
     the coordinates in ascending order in every sweep and each column stops on its own ``tol`` test, so
     ``W`` is a function of the arguments alone (``n_threads`` does not change it; see
     :func:`irspack_amd.utils.slim_weight_allow_negative`).  ``W`` is a float32 ``csc_matrix``."""
+
+    default_tune_range = [LogUniformFloatRange("alpha", 1e-5, 1), UniformFloatRange("l1_ratio", 0, 1)]
 
     def __init__(self, X_train_all: Any, alpha: float = 0.05, l1_ratio: float = 0.01,
                  positive_only: bool = True, n_iter: int = 100, tol: float = 1e-4,

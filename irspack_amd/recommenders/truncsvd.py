@@ -8,6 +8,7 @@ from typing import Any, Optional
 import numpy as np
 import scipy.sparse as sps
 
+from ..optimization.parameter_range import UniformIntegerRange
 from ..utils import truncated_svd
 from .base import BaseRecommender
 
@@ -28,6 +29,8 @@ class TruncatedSVDDecomposer:
 
 
 class TruncatedSVDRecommender(BaseRecommender):
+    default_tune_range = [UniformIntegerRange("n_components", 4, 512)]
+
     def __init__(self, X_train_all: Any, n_components: int = 4, random_seed: int = 0) -> None:
         assert X_train_all.shape[1] > 1
         super().__init__(X_train_all)

@@ -11,6 +11,8 @@ computer built on ``X_weighted`` (users are the rows: no transpose, unlike item-
 from typing import Any, Optional
 
 from .._threading import get_n_threads
+from ..optimization.parameter_range import (CategoricalRange, UniformFloatRange,
+                                            default_tune_range_knn_with_weighting)
 from ..utils import remove_diagonal
 from ._knn import AsymmetricSimilarityComputer, CosineSimilarityComputer
 from .base import BaseUserSimilarityRecommender
@@ -49,6 +51,8 @@ class BaseUserKNNRecommender(BaseUserSimilarityRecommender):
 
 
 class CosineUserKNNRecommender(BaseUserKNNRecommender):  # user_knn.py:81-148 (normalize defaults to True)
+    default_tune_range = default_tune_range_knn_with_weighting + [CategoricalRange("normalize", [False, True])]
+
     def __init__(self, X_train_all: Any, shrinkage: float = 0.0, normalize: bool = True,
                  top_k: int = 100, feature_weighting: str = "NONE", bm25_k1: float = 1.2,
                  bm25_b: float = 0.75, n_threads: Optional[int] = None) -> None:
@@ -60,6 +64,8 @@ class CosineUserKNNRecommender(BaseUserKNNRecommender):  # user_knn.py:81-148 (n
 
 
 class AsymmetricCosineUserKNNRecommender(BaseUserKNNRecommender):  # user_knn.py:155-218
+    default_tune_range = default_tune_range_knn_with_weighting + [UniformFloatRange("alpha", 0, 1)]
+
     def __init__(self, X_train_all: Any, shrinkage: float = 0.0, alpha: float = 0.5,
                  top_k: int = 100, feature_weighting: str = "NONE", bm25_k1: float = 1.2,
                  bm25_b: float = 0.75, n_threads: Optional[int] = None) -> None:
