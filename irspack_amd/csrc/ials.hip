@@ -776,6 +776,8 @@ void launch_ialspp(irs_ials_trainer *t, Side &sd, const float *other, float *tar
 //                               fp32-input matrix instruction.  Default (round 6): the bf16 matrix cores
 //                               on exact three-way splits of the fp32 values, six fp32-exact partial
 //                               products per product, fp32 accumulate (syrk_gather_bf16x3, ials_kernels.hpp)
+//   IRSPACK_AMD_IALS_GATHER_LDS=0  the bf16x3 Cholesky kernel at K <= 64 keeps its gathered rows in registers (three
+//                               waves per SIMD) instead of staging them in LDS (four; syrk_gather_bf16x3_lds)
 void read_switches(irs_ials_trainer *t) {
   t->opt_wave128 = env_flag("IRSPACK_AMD_IALS_WAVE128", true);
   t->opt_unit = env_flag("IRSPACK_AMD_IALS_UNIT", true);
@@ -786,6 +788,7 @@ void read_switches(irs_ials_trainer *t) {
   t->opt_pp_fork = env_flag("IRSPACK_AMD_IALSPP_FORK", true);
   t->opt_wg16 = env_flag("IRSPACK_AMD_IALS_WG16", true);
   t->opt_bf16x3 = env_flag("IRSPACK_AMD_IALS_BF16X3", true);
+  t->opt_gather_lds = env_flag("IRSPACK_AMD_IALS_GATHER_LDS", true);
   t->opt_eig = env_flag("IRSPACK_AMD_IALS_EIG", true);
   t->opt_mf = env_flag("IRSPACK_AMD_IALS_MF", true);
 }
@@ -1258,6 +1261,7 @@ void launch_solve(irs_ials_trainer *t, Side &sd, const float *other, float *targ
           else if (r.cg && x3) k = ials_solve_kernel<4, 1, 0, true, true>;
           else if (r.cg && r.unit) k = ials_solve_kernel<TT, 1, 0, true>;
           else if (r.cg) k = ials_solve_kernel<TT, 1, 0>;
+          else if (x3 && r.x3_lds) k = ials_solve_kernel<4, 0, 0, true, true, false, true>;
           else if (x3) k = ials_solve_kernel<4, 0, 0, true, true>;
           else if (r.unit) k = ials_solve_kernel<TT, 0, 0, true>;
           else k = ials_solve_kernel<TT, 0, 0>;

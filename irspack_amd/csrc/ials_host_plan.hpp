@@ -169,6 +169,7 @@ struct Switches {
   bool opt_pp_chain = true;   // iALS++ prediction passes merged into the rank updates (IRSPACK_AMD_IALSPP_CHAIN)
   bool opt_pp_fork = true;    // iALS++ short-row launch on a second stream (IRSPACK_AMD_IALSPP_FORK)
   bool opt_bf16x3 = false;
+  bool opt_gather_lds = false;  // the bf16x3 gather staged in LDS (IRSPACK_AMD_IALS_GATHER_LDS)
   bool opt_eig = true, opt_mf = true;  // IRSPACK_AMD_IALS_EIG, IRSPACK_AMD_IALS_MF
 };
 // what launch_solve knows before it launches anything
@@ -212,6 +213,12 @@ inline PpVariant pp_variant(uint64_t subspace_dimension, int64_t K, int KP, bool
   return v;
 }
 
+// The LDS-staged gather keeps ONE 8-KB group per wave in flight (16 waves per CU) where the register-staged one
+// keeps two (12 waves): faster while the gathered table is served by L2, slower beyond.  ML-20M shape, K = 64, one
+// MI355X: the 6.8 MB item table 1.067 -> 1.045 ms (user half), the 35 MB user table 0.617 -> 0.625 ms (item half);
+// nothing was measured in between, the limit is set between the two at four times an XCD's L2.
+constexpr uint64_t GATHER_LDS_MAX_TABLE_BYTES = uint64_t(16) << 20;
+
 enum class SolvePath : int32_t {
   PP_BLOCKS,   // iALS++ sweeps over blocks of up to 64 dims (ials_pp_kernels.hpp)
   PP_GENERAL,  // iALS++ with wider blocks or KP > 2048 (ials_gk_kernels.hpp)
@@ -234,6 +241,10 @@ struct SolveRoute {
   // the bf16x3 rank update of: the launch over the regular tasks; the launch that finishes the split rows (CG only:
   // lower-form partials); a dense launch over the short rows after the eigenbasis path declined
   bool x3, x3_split, x3_declined;
+  // the bf16x3 launches over tasks stage their gathered rows in LDS instead of registers (Cholesky at T = 4: the
+  // CG kernel keeps its matrix rows in 64 registers and gains no wave from the 48 the staging frees), where the
+  // gathered table is at most GATHER_LDS_MAX_TABLE_BYTES
+  bool x3_lds;
   bool short_cg_ok, short_fork;  // the short rows take the matrix-free short-row CG kernels; on the second stream
   bool eig_candidate;  // the eigenbasis path for the short rows is worth trying (then P's conditioning decides)
   int32_t n_regular;   // tasks of the dense launch: all, or all but the short rows
@@ -281,6 +292,8 @@ inline SolveRoute solve_route(const SolveFacts &f) {
   if (r.family == DenseFamily::WAVE) {
     r.x3 = r.x3_declined = r.unit && f.opt_bf16x3 && f.T == 4;
     r.x3_split = r.x3 && r.cg;
+    r.x3_lds = r.x3 && !r.cg && !r.pp_direct && f.opt_gather_lds &&
+               static_cast<uint64_t>(f.n_other) * f.KP * sizeof(float) <= GATHER_LDS_MAX_TABLE_BYTES;
   } else if (r.family == DenseFamily::WAVE8) {
     // The bf16x3 kernels hold ~410-440 registers (one wave per SIMD), the fp32-input Cholesky kernel 236 (two).
     // Under Cholesky the second wave is worth more than the faster rank update when rows are short - ML-20M user

@@ -479,6 +479,94 @@ __device__ __forceinline__ unsigned pack_bf16(float a, float b) {  // v_cvt_pk_b
   return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, bf16x2_t));
 }
 
+// The pieces of one 32-entry group of the bf16x3 rank update; `raw[kk]` = this lane's dims of entry 8 g + kk.
+// bf16x3_split: dim d of the eight entries is summed into bsum and split; bf16x3_tile: the six products of tile
+// (row block j, column block i), smallest terms first.  Tiles are independent accumulators, so the order of the
+// tiles among themselves does not change a bit; the order inside a tile and the order of the groups do.
+template <int T, bool RESID>
+__device__ __forceinline__ void bf16x3_split(const f32x4 (&raw)[8][T / 4], int d, const float (&w8)[RESID ? 8 : 1],
+                                             u32x4_t (&hi)[T], u32x4_t (&mid)[T], u32x4_t (&lo)[T], float (&bsum)[T]) {
+#pragma unroll
+  for (int pp = 0; pp < 4; pp++) {
+    const float x0 = raw[2 * pp][d >> 2][d & 3], x1 = raw[2 * pp + 1][d >> 2][d & 3];
+    if constexpr (RESID) bsum[d] = fmaf(w8[2 * pp + 1], x1, fmaf(w8[2 * pp], x0, bsum[d]));
+    else bsum[d] += x0 + x1;
+    const unsigned h = pack_bf16(x0, x1);
+    const float r0 = x0 - __uint_as_float(h << 16), r1 = x1 - __uint_as_float(h & 0xffff0000u);
+    const unsigned mi = pack_bf16(r0, r1);
+    const float s0 = r0 - __uint_as_float(mi << 16), s1 = r1 - __uint_as_float(mi & 0xffff0000u);
+    hi[d][pp] = h;
+    mid[d][pp] = mi;
+    lo[d][pp] = pack_bf16(s0, s1);
+  }
+}
+template <int T>
+__device__ __forceinline__ void bf16x3_tile(f32x4 &acc, const u32x4_t (&hi)[T], const u32x4_t (&mid)[T],
+                                            const u32x4_t (&lo)[T], int j, int i) {
+  const bf16x8_t ah = __builtin_bit_cast(bf16x8_t, hi[j]), am = __builtin_bit_cast(bf16x8_t, mid[j]),
+                 al = __builtin_bit_cast(bf16x8_t, lo[j]);
+  const bf16x8_t bh = __builtin_bit_cast(bf16x8_t, hi[i]), bm = __builtin_bit_cast(bf16x8_t, mid[i]),
+                 bl = __builtin_bit_cast(bf16x8_t, lo[i]);
+  // smallest terms first
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bm, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bh, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bm, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, acc, 0, 0, 0);
+}
+// The whole group, every split before the first product (the register-staged gather).
+template <int T, bool RESID>
+__device__ __forceinline__ void bf16x3_group(const f32x4 (&raw)[8][T / 4], const float (&xr)[T], float bias,
+                                             f32x4 (&acc)[Geo<T>::NT], float (&bsum)[T]) {
+  u32x4_t hi[T], mid[T], lo[T];
+  float w8[RESID ? 8 : 1];
+  if constexpr (RESID) {
+#pragma unroll
+    for (int kk = 0; kk < 8; kk++) {
+      float d = 0.f;  // the prediction v_q . x (hpp:455-457); a zero row (past the row's end) predicts 0 and adds 0
+#pragma unroll
+      for (int dd = 0; dd < T; dd++) d = fmaf(raw[kk][dd >> 2][dd & 3], xr[dd], d);
+      w8[kk] = (bias + 1.0f) - row16_sum(d);
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < T; d++) bf16x3_split<T, RESID>(raw, d, w8, hi, mid, lo, bsum);
+  int t = 0;
+#pragma unroll
+  for (int i = 0; i < T; i++)
+#pragma unroll
+    for (int j = i; j < T; j++) bf16x3_tile<T>(acc[t++], hi, mid, lo, j, i);  // tile (row block j, column block i)
+}
+// scheduling groups: (one matrix instruction, NV vector instructions) sizeof...(I) times
+template <int NV, int... I> __device__ __forceinline__ void interleave_mfma_valu(std::integer_sequence<int, I...>) {
+  ((void)I, ..., (__builtin_amdgcn_sched_group_barrier(0x008, 1, 0), __builtin_amdgcn_sched_group_barrier(0x002, NV, 0)));
+}
+// The same group by row blocks: the tiles of row block d need the dims up to d only, so their products are issued
+// as soon as dim d is split and run on the matrix pipe under the split of dim d + 1 (the LDS-staged gather).  The
+// scheduling groups pin that order: left alone hipcc issues all four splits, then the 60 products back to back.
+template <int T>
+__device__ __forceinline__ void bf16x3_group_by_rows(const f32x4 (&raw)[8][T / 4], f32x4 (&acc)[Geo<T>::NT],
+                                                     float (&bsum)[T]) {
+  u32x4_t hi[T], mid[T], lo[T];
+  const float w8[1] = {};
+  bf16x3_split<T, false>(raw, 0, w8, hi, mid, lo, bsum);
+#pragma unroll
+  for (int d = 0; d < T; d++) {
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i <= d; i++) bf16x3_tile<T>(acc[i * T - i * (i - 1) / 2 + (d - i)], hi, mid, lo, d, i);
+    if (d + 1 < T) {
+      bf16x3_split<T, false>(raw, d + 1, w8, hi, mid, lo, bsum);
+      // one matrix instruction, then its share of the ~52 vector instructions of the split
+      if (d == 0) interleave_mfma_valu<9>(std::make_integer_sequence<int, 6>{});
+      else if (d == 1) interleave_mfma_valu<5>(std::make_integer_sequence<int, 12>{});
+      else interleave_mfma_valu<3>(std::make_integer_sequence<int, 18>{});
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+}
+
 // RESID (the one-block iALS++ sweep, see syrk_gather_impl): the right-hand side is the negative gradient at
 // the current row `xr`, built from the predictions d_q = v_q . x - from the gathered fp32 values, before
 // they are split: sum_q ((bias + 1) - d_q) v_q; the 16 lanes of a group share the group's eight entries, so
@@ -521,53 +609,7 @@ __device__ __forceinline__ void syrk_gather_bf16x3(const float *__restrict__ oth
       }
     }
   };
-  auto consume = [&](int slot) {
-    u32x4_t hi[T], mid[T], lo[T];
-    float w8[RESID ? 8 : 1];
-    if constexpr (RESID) {
-#pragma unroll
-      for (int kk = 0; kk < 8; kk++) {
-        float d = 0.f;  // the prediction v_q . x (hpp:455-457); a zero row (past the row's end) predicts 0 and adds 0
-#pragma unroll
-        for (int dd = 0; dd < T; dd++) d = fmaf(raw[slot][kk][dd >> 2][dd & 3], xr[dd], d);
-        w8[kk] = (bias + 1.0f) - row16_sum(d);
-      }
-    }
-#pragma unroll
-    for (int d = 0; d < T; d++) {
-#pragma unroll
-      for (int pp = 0; pp < 4; pp++) {
-        const float x0 = raw[slot][2 * pp][d >> 2][d & 3], x1 = raw[slot][2 * pp + 1][d >> 2][d & 3];
-        if constexpr (RESID) bsum[d] = fmaf(w8[2 * pp + 1], x1, fmaf(w8[2 * pp], x0, bsum[d]));
-        else bsum[d] += x0 + x1;
-        const unsigned h = pack_bf16(x0, x1);
-        const float r0 = x0 - __uint_as_float(h << 16), r1 = x1 - __uint_as_float(h & 0xffff0000u);
-        const unsigned mi = pack_bf16(r0, r1);
-        const float s0 = r0 - __uint_as_float(mi << 16), s1 = r1 - __uint_as_float(mi & 0xffff0000u);
-        hi[d][pp] = h;
-        mid[d][pp] = mi;
-        lo[d][pp] = pack_bf16(s0, s1);
-      }
-    }
-    int t = 0;
-#pragma unroll
-    for (int i = 0; i < T; i++)
-#pragma unroll
-      for (int j = i; j < T; j++) {  // tile (row block j, column block i)
-        const bf16x8_t ah = __builtin_bit_cast(bf16x8_t, hi[j]), am = __builtin_bit_cast(bf16x8_t, mid[j]),
-                       al = __builtin_bit_cast(bf16x8_t, lo[j]);
-        const bf16x8_t bh = __builtin_bit_cast(bf16x8_t, hi[i]), bm = __builtin_bit_cast(bf16x8_t, mid[i]),
-                       bl = __builtin_bit_cast(bf16x8_t, lo[i]);
-        // smallest terms first
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bm, acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bh, acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bm, acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, acc[t], 0, 0, 0);
-        t++;
-      }
-  };
+  auto consume = [&](int slot) { bf16x3_group<T, RESID>(raw[slot], xr, bias, acc, bsum); };
   // index blocks of 64 entries, one per lane, two blocks ahead (padded arrays: every load is
   // unconditional, the loop is one basic block)
   const int zr = static_cast<int>(zero_row);
@@ -601,6 +643,114 @@ __device__ __forceinline__ void syrk_gather_bf16x3(const float *__restrict__ oth
     bsum[i] += __shfl_xor(bsum[i], 16, 64);
     bsum[i] += __shfl_xor(bsum[i], 32, 64);
     if constexpr (!RESID) bsum[i] *= bias + 1.0f;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// The same gather staged in LDS (T = 4, IRSPACK_AMD_IALS_GATHER_LDS): the group in flight lives in the wave's solve
+// scratch, which is dead during the rank update, instead of in 64 registers - the kernel then fits 128 registers,
+// four waves per SIMD.  gfx950's 16-byte direct-to-LDS load writes wave-uniform base + 16 lane: lane (g, m) fetches
+// dims 4 m .. 4 m + 3 of entry 8 g + kk, so piece kk of a group (one wave instruction, 1 KiB) is four whole rows, and
+// every lane reads back exactly the 16 bytes it fetched (ds_read_b128 at 16 lane: no bank conflict, and no other
+// wave or lane ever reads them - the issuing wave's own counted wait orders the read, no barrier).
+//   ring   sm[0, 2048)     one group = 8 pieces
+//   islot  sm[2048, 2112)  the next 64-entry index block, one 4-byte direct-to-LDS load per lane
+// The index stream goes through LDS too: the use of an ordinary global load's result while direct-to-LDS loads are
+// pending makes hipcc wait vmcnt(0).  hipcc places no wait of its own between a direct-to-LDS load and the ds_read
+// of its bytes, and none between a ds_read and the load that overwrites its source: every wait below is explicit.
+//   GLDS_WAIT_LANDED   every direct-to-LDS load this wave issued has written LDS.  The queue holds exactly the group
+//                      about to be read (and the index block issued before it), so the count is 0 by construction.
+//   GLDS_WAIT_READ     the ds_reads of a slot have returned: only then is the slot refilled.
+// Nothing is issued that is not consumed, and the last wait is behind the last issue: the solve and the partial
+// store find the scratch quiet.  Groups, splits, the products inside a tile and bsum run in the order of
+// syrk_gather_bf16x3; the tiles, independent accumulators, run by row blocks (bf16x3_group_by_rows): the same bits.
+#define GLDS_WAIT_LANDED() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+#define GLDS_WAIT_READ() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
+constexpr int GLDS_RING_FLOATS = 8 * 256, GLDS_FLOATS = GLDS_RING_FLOATS + 64;
+
+template <int BYTES> __device__ __forceinline__ void glds_load(const void *src, float *dst_wave_uniform) {
+  static_assert(BYTES == 4 || BYTES == 16, "global_load_lds_dword / _dwordx4");
+  const auto gsrc = (const __attribute__((address_space(1))) void *)src;
+  const auto ldst = (__attribute__((address_space(3))) void *)dst_wave_uniform;
+  // (the size must be a literal to the front end)
+  if constexpr (BYTES == 16) __builtin_amdgcn_global_load_lds(gsrc, ldst, 16, 0, 0);
+  else __builtin_amdgcn_global_load_lds(gsrc, ldst, 4, 0, 0);
+}
+
+template <int T>
+__device__ __forceinline__ void syrk_gather_bf16x3_lds(const float *__restrict__ other,
+                                                       const int32_t *__restrict__ indices, int begin, int end,
+                                                       float bias, f32x4 (&acc)[Geo<T>::NT], float (&bsum)[T],
+                                                       unsigned zero_row, float *sm) {
+  static_assert(T == 4, "one 16-byte piece per lane and entry");
+  constexpr int KP = Geo<T>::KP;
+  const int lane = threadIdx.x & 63;
+  const int g = lane >> 4, m = lane & 15;
+  const int n = end - begin;
+  const int ngroups = (n + 31) >> 5;
+  const uint32_t lane_off = static_cast<uint32_t>(T * m * sizeof(float));
+  const int32_t *ip = indices + begin + lane;
+  float *islot = sm + GLDS_RING_FLOATS;
+  // entries 32 gi + 8 g + kk of the 64-entry index block held one per lane in blk_idx (entries past the row's end
+  // were replaced by the zero row when the block was read: every address is valid)
+  auto issue = [&](int blk_idx, int gi) {
+#pragma unroll
+    for (int kk = 0; kk < 8; kk++) {
+      const int src = 4 * (32 * gi + 8 * g + kk);
+      const unsigned idx = static_cast<unsigned>(__builtin_amdgcn_ds_bpermute(src, blk_idx));
+      const uint32_t off = idx * static_cast<uint32_t>(KP * sizeof(float)) + lane_off;
+      glds_load<16>(reinterpret_cast<const char *>(other) + off, sm + 256 * kk);
+    }
+  };
+  auto take = [&](f32x4 (&raw)[8][1]) {
+#pragma unroll
+    for (int kk = 0; kk < 8; kk++) raw[kk][0] = *reinterpret_cast<const f32x4 *>(sm + 256 * kk + 4 * lane);
+  };
+  if (ngroups > 0) {
+    const int zr = static_cast<int>(zero_row);
+    int cur = ip[0];  // (an ordinary load: nothing is in flight yet)
+    cur = lane < n ? cur : zr;
+    issue(cur, 0);
+    glds_load<4>(ip + 64, islot);
+    int g0 = 0;
+    f32x4 raw[8][1];
+    // two groups = one index block per round; a round issues the two groups behind its own, so it runs only
+    // while both exist (the loop is one basic block)
+    for (; g0 + 3 <= ngroups; g0 += 2) {
+      GLDS_WAIT_LANDED();
+      take(raw);
+      int nxt = __float_as_int(islot[lane]);
+      GLDS_WAIT_READ();
+      nxt = 32 * (g0 + 2) + lane < n ? nxt : zr;
+      glds_load<4>(ip + 32 * (g0 + 2) + 64, islot);  // the block after the next one
+      issue(cur, 1);
+      bf16x3_group_by_rows<T>(raw, acc, bsum);
+      GLDS_WAIT_LANDED();
+      take(raw);
+      GLDS_WAIT_READ();
+      issue(nxt, 0);
+      bf16x3_group_by_rows<T>(raw, acc, bsum);
+      cur = nxt;
+    }
+    // the last one or two groups, both of block `cur`
+    const bool two = g0 + 2 <= ngroups;
+    GLDS_WAIT_LANDED();
+    take(raw);
+    GLDS_WAIT_READ();
+    if (two) issue(cur, 1);
+    bf16x3_group_by_rows<T>(raw, acc, bsum);
+    if (two) {
+      GLDS_WAIT_LANDED();
+      take(raw);
+      GLDS_WAIT_READ();
+      bf16x3_group_by_rows<T>(raw, acc, bsum);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < T; i++) {
+    bsum[i] += __shfl_xor(bsum[i], 16, 64);
+    bsum[i] += __shfl_xor(bsum[i], 32, 64);
+    bsum[i] *= bias + 1.0f;
   }
 }
 
@@ -1111,14 +1261,19 @@ template <int T> __device__ __forceinline__ void resid_add_step(float *xrow, con
 
 // RESID: the one-block iALS++ sweep (see syrk_gather_impl): right-hand side = negative gradient at the
 // current row, solution = the step; SOLVER 0, T <= 4.
-template <int T, int SOLVER, int MODE, bool UNIT = false, bool BF16X3 = false, bool RESID = false>
-__global__ __launch_bounds__(64 * SOLVE_WAVES, (T > 4 && (SOLVER == 1 || BF16X3)) ? 1 : (T <= 4 ? (RESID && MODE == 0 ? (UNIT ? 3 : 4) : (BF16X3 && MODE == 0 ? 3 : SOLVE_MIN_WAVES_PER_SIMD_K64)) : SOLVE_MIN_WAVES_PER_SIMD)) void ials_solve_kernel(SolveParams p) {
+// GLDS: the bf16x3 gather staged in LDS (syrk_gather_bf16x3_lds: T = 4, Cholesky, MODE 0), four waves per SIMD.
+#ifndef IRS_GLDS_WAVES_PER_SIMD
+#define IRS_GLDS_WAVES_PER_SIMD 4
+#endif
+template <int T, int SOLVER, int MODE, bool UNIT = false, bool BF16X3 = false, bool RESID = false, bool GLDS = false>
+__global__ __launch_bounds__(64 * SOLVE_WAVES, GLDS ? IRS_GLDS_WAVES_PER_SIMD : (T > 4 && (SOLVER == 1 || BF16X3)) ? 1 : (T <= 4 ? (RESID && MODE == 0 ? (UNIT ? 3 : 4) : (BF16X3 && MODE == 0 ? 3 : SOLVE_MIN_WAVES_PER_SIMD_K64)) : SOLVE_MIN_WAVES_PER_SIMD)) void ials_solve_kernel(SolveParams p) {
   // bf16x3: unit confidences, K <= 64 padded to 64; Cholesky (whose split rows' second pass is the plain MODE 1
   // kernel: both work on lower tiles) and, round 6, CG on the explicit system (MODE 1 with BF16X3 = "the
   // partials and the Gramian are lower-form tiles")
   static_assert(!BF16X3 || ((T == 4 || T == 8) && (MODE == 1 ? SOLVER == 1 : UNIT)),
                 "bf16x3: unit confidences at 48 < K <= 64 and 64 < K <= 128");
   static_assert(!RESID || (SOLVER == 0 && T <= 4), "the gradient form: Cholesky at K <= 64");
+  static_assert(!GLDS || (BF16X3 && T == 4 && SOLVER == 0 && MODE == 0 && !RESID), "the LDS-staged gather: Cholesky, K <= 64");
   constexpr int WAVES = SOLVE_WAVES;
   using G = Geo<T>;
   // Cholesky: lower-form tiles + the 16-row block solve of ials_chol16.hpp
@@ -1127,6 +1282,7 @@ __global__ __launch_bounds__(64 * SOLVE_WAVES, (T > 4 && (SOLVER == 1 || BF16X3)
   constexpr int LDS_PER_WAVE = SOLVER == 0 ? Chol16Geo<T>::LDS_FLOATS
                                            : (T == 8 ? CholGeo<T>::SPILL_CG_FLOATS : G::CG_LDS_FLOATS);
   __shared__ __attribute__((aligned(16))) float lds[WAVES * LDS_PER_WAVE];
+  static_assert(!GLDS || GLDS_FLOATS <= LDS_PER_WAVE, "the gather ring overlays the solve scratch");
   // (K = 128: with the scalar task the register allocator spills 800 bytes per lane where the
   // per-lane form spills 12 - the two starts of the accumulators become real branches)
   const int wid = T <= 4 ? wave_in_block() : static_cast<int>(threadIdx.x >> 6);
@@ -1153,7 +1309,10 @@ __global__ __launch_bounds__(64 * SOLVE_WAVES, (T > 4 && (SOLVER == 1 || BF16X3)
     }
     float xr[T] = {};
     if constexpr (RESID) load_dims<T>(p.target + static_cast<size_t>(task.row) * G::KP + T * (lane & 15), xr);
-    if constexpr (BF16X3)
+    if constexpr (GLDS)
+      syrk_gather_bf16x3_lds<T>(p.other, p.indices, task.begin, task.end, p.bias, acc, bsum,
+                                static_cast<unsigned>(p.zero_row), sm);
+    else if constexpr (BF16X3)
       syrk_gather_bf16x3<T, RESID>(p.other, p.indices, task.begin, task.end, p.bias, acc, bsum,
                                    static_cast<unsigned>(p.zero_row), xr);
     else
