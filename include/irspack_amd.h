@@ -986,6 +986,33 @@ irs_status irs_serve_recommend_factors(irs_server *s, int64_t rows, const float 
                                        const int64_t *excl_indptr, const int32_t *excl_indices, int64_t n_lists,
                                        const int64_t *list_ptr, const int64_t *list_items, int64_t cutoff,
                                        int32_t *out_idx, float *out_score, int32_t *out_len);
+/* Neighbours: "entities like ids[r]", ranked inside the resident operand (no reference counterpart).  Row r of
+ * the call scores every entity j of the server against ids[r] (int64 [rows], each in [0, n_items), repeats
+ * allowed); the entity itself is always excluded (score -inf), also when an allowed list names it.  Outputs,
+ * allowed lists, exclusions, chunking, ties, threads and "two calls give identical bytes" are those of the
+ * recommend calls above, word for word; every argument error (IRS_INVALID_ARGUMENT: an id out of range, a metric
+ * that does not fit the server, k_used outside 1 .. k on a factor server or != 0 on a similarity server, a
+ * similarity server whose W is not square) comes before any device work.  Nothing but the ids, the exclusions
+ * and the lists is uploaded.
+ *   similarity servers, IRS_NEIGHBOR_WEIGHT (float64 scores): score[r, j] = W[ids[r], j].  Sparse W: only the
+ *     STORED entries of the row are candidates (stored zeros included, any order) - an item without a stored
+ *     weight is never listed, which is where the call differs from recommending for a one-hot profile.  Dense
+ *     W: the whole row (float32 widened exactly).
+ *   factor servers (float32 scores through the MFMA tiles), over the leading k_used columns of the table only
+ *     (a bias column or a constant column of the model's table is left out this way):
+ *     IRS_NEIGHBOR_DOT     v_q . v_j
+ *     IRS_NEIGHBOR_COSINE  (v_q / |v_q|) . v_j / |v_j|: one inverse norm per table row - sum of squares and
+ *                          1/sqrt in double, rounded once to float32 - made at the first cosine call, kept on
+ *                          the server and remade when k_used changes.  A candidate of norm zero is never listed;
+ *                          a query of norm zero gets an empty list.
+ *   Tables are finite, as for the recommend calls. */
+#define IRS_NEIGHBOR_WEIGHT 0 /* similarity servers */
+#define IRS_NEIGHBOR_COSINE 1 /* factor servers */
+#define IRS_NEIGHBOR_DOT 2    /* factor servers */
+irs_status irs_serve_neighbors(irs_server *s, int64_t rows, const int64_t *ids, int32_t metric, int32_t k_used,
+                               const int64_t *excl_indptr, const int32_t *excl_indices, int64_t n_lists,
+                               const int64_t *list_ptr, const int64_t *list_items, int64_t cutoff,
+                               int32_t *out_idx, float *out_score, int32_t *out_len);
 /* Stream time of the last recommend call by phase, in milliseconds (measurement only): ms[0] uploads,
  * ms[1] scoring, ms[2] exclusions, ms[3] ranking, the output stage and the copies home. */
 irs_status irs_serve_last_phases(irs_server *s, double *ms);

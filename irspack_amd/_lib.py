@@ -197,6 +197,8 @@ class SplitStatsStruct(C.Structure):  # irs_split_stats
 SPLIT_BY_RATIO, SPLIT_BY_FIXED_N = 0, 1  # IRS_SPLIT_BY_* of include/irspack_amd.h
 
 ABI_VERSION = 4  # IRS_ABI_VERSION of include/irspack_amd.h
+# the metrics of irs_serve_neighbors
+NEIGHBOR_WEIGHT, NEIGHBOR_COSINE, NEIGHBOR_DOT = 0, 1, 2
 # IRS_EXCHANGE_* of include/irspack_amd.h: how irs_ials_sharded_step moves the solved rows
 EXCHANGE_MODES = {"auto": 0, "broadcast": 1, "mesh": 2, "peer": 3}
 COMM_HANDLE_BYTES = 256
@@ -321,6 +323,7 @@ EXPORTED_SYMBOLS = [
     "irs_serve_destroy",
     "irs_serve_recommend_profiles",
     "irs_serve_recommend_factors",
+    "irs_serve_neighbors",
     "irs_serve_last_phases",
     "irs_measure_ceilings",
 ]
@@ -434,6 +437,10 @@ ARGTYPES = {
     "irs_serve_recommend_factors": [
         C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int64,
         C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_float),
+        C.POINTER(C.c_int32)],
+    "irs_serve_neighbors": [
+        C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+        C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_float),
         C.POINTER(C.c_int32)],
     "irs_serve_last_phases": [C.c_void_p, C.POINTER(C.c_double)],
 }

@@ -1,11 +1,12 @@
 // Serving: irs_serve_* (include/irspack_amd.h).  The item-side operand lives in an irs_server; a recommend call
-// uploads its rows, then per chunk: score, mask, rank (retrieve = 1), emit (serve_kernels.hpp).
+// uploads its rows, then per chunk: score, mask, rank (retrieve = 1), emit (serve_kernels.hpp).  A neighbour call
+// (irs_serve_neighbors) uploads only ids and scores them against the resident operand itself; the rest is the same.
 // (Included by evaluator.hip at the end of its translation unit: the calls use its host helpers and kernels.)
 #pragma once
 
 namespace {
 
-// what the two recommend calls share
+// what the two recommend calls and the neighbour call share
 struct ServeCall {
   int64_t rows;
   const int64_t *excl_indptr;
@@ -272,6 +273,78 @@ irs_status irs_serve_recommend_factors(irs_server *sv, int64_t rows, const float
     serve_run<float>(sv, c, s, clock, [&](int64_t b, int64_t m, float *block) {
       if (irs_gk_scores_device_(sv->user.ptr + b * KP, sv->item.ptr, KP, m, ni, block, ni, s) != IRS_OK)
         throw std::runtime_error(irs_last_error());
+    });
+  });
+}
+
+irs_status irs_serve_neighbors(irs_server *sv, int64_t rows, const int64_t *ids, int32_t metric, int32_t k_used,
+                               const int64_t *excl_indptr, const int32_t *excl_indices, int64_t n_lists,
+                               const int64_t *list_ptr, const int64_t *list_items, int64_t cutoff, int32_t *out_idx,
+                               float *out_score, int32_t *out_len) {
+  return guard([&] {
+    check_arg(sv != nullptr, "null argument.");
+    const int64_t ni = sv->n_items;
+    const bool factors = sv->kind == irs_server::FACTORS;
+    if (factors) {
+      check_arg(metric == IRS_NEIGHBOR_COSINE || metric == IRS_NEIGHBOR_DOT,
+                "this server holds factors: the metric is IRS_NEIGHBOR_COSINE or IRS_NEIGHBOR_DOT.");
+      check_arg(k_used >= 1 && k_used <= sv->k, "k_used must lie in 1 .. k.");
+    } else {
+      check_arg(metric == IRS_NEIGHBOR_WEIGHT, "this server holds similarity weights: the metric is IRS_NEIGHBOR_WEIGHT.");
+      check_arg(k_used == 0, "k_used must be 0 on a similarity server.");
+      check_arg(sv->n_profile_cols == ni, "neighbours need a square W.");
+    }
+    ServeCall c{rows, excl_indptr, excl_indices, n_lists, list_ptr, list_items, cutoff, out_idx, out_score, out_len};
+    check_arg(rows <= 0 || ids != nullptr, "null argument.");
+    for (int64_t r = 0; r < rows; r++) check_arg(ids[r] >= 0 && ids[r] < ni, "neighbour id out of range.");
+    if (!serve_check(sv, c)) return;
+    std::lock_guard<std::mutex> one_call(sv->call_mutex);  // (the call scratch is the handle's)
+    IRS_HIP(hipSetDevice(sv->device));
+    hipStream_t s = nullptr;
+    PhaseClock clock(s);
+    sv->nb_ids.upload(ids, static_cast<size_t>(rows), s);
+    const int64_t *d_ids = sv->nb_ids.ptr;
+    if (!factors) {
+      serve_run<double>(sv, c, s, clock, [&](int64_t b, int64_t m, double *block) {
+        const dim3 grid(static_cast<unsigned>(m)), wg(NB_THREADS);
+        if (sv->kind == irs_server::SPARSE)
+          hipLaunchKernelGGL(nb_sparse_rows_kernel, grid, wg, 0, s, block, m, ni, d_ids + b,
+                             static_cast<const int64_t *>(sv->w_ptr.ptr), static_cast<const int32_t *>(sv->w_idx.ptr),
+                             static_cast<const double *>(sv->w_val.ptr));
+        else if (sv->w_is_f64)
+          hipLaunchKernelGGL(nb_dense_rows_kernel<double>, grid, wg, 0, s, block, m, ni, d_ids + b,
+                             reinterpret_cast<const double *>(sv->w_dense.ptr));
+        else
+          hipLaunchKernelGGL(nb_dense_rows_kernel<float>, grid, wg, 0, s, block, m, ni, d_ids + b,
+                             reinterpret_cast<const float *>(sv->w_dense.ptr));
+      });
+      return;
+    }
+    const int32_t KP = sv->KP;
+    const float *inv = nullptr;
+    if (metric == IRS_NEIGHBOR_COSINE) {
+      if (sv->inv_norm_k != k_used) {
+        sv->inv_norm_k = 0;
+        sv->inv_norm.alloc(static_cast<size_t>(ni));
+        hipLaunchKernelGGL(nb_inv_norm_kernel, dim3(static_cast<unsigned>(ceil_div(ni, NB_ROWS_PER_BLOCK))),
+                           dim3(NB_THREADS), 0, s, static_cast<const float *>(sv->item.ptr), ni, KP, k_used,
+                           sv->inv_norm.ptr);
+        IRS_HIP(hipGetLastError());
+        sv->inv_norm_k = k_used;
+      }
+      inv = sv->inv_norm.ptr;
+    }
+    // the query block [rows, KP] out of the resident table (scaled for cosine, zero from k_used on)
+    sv->user.alloc(static_cast<size_t>(rows) * KP);
+    hipLaunchKernelGGL(nb_gather_kernel, dim3(static_cast<unsigned>(ceil_div(rows, NB_ROWS_PER_BLOCK))),
+                       dim3(NB_THREADS), 0, s, static_cast<const float *>(sv->item.ptr), d_ids, rows, KP, k_used, inv,
+                       sv->user.ptr);
+    IRS_HIP(hipGetLastError());
+    serve_run<float>(sv, c, s, clock, [&](int64_t b, int64_t m, float *block) {
+      if (irs_gk_scores_device_(sv->user.ptr + b * KP, sv->item.ptr, KP, m, ni, block, ni, s) != IRS_OK)
+        throw std::runtime_error(irs_last_error());
+      hipLaunchKernelGGL(nb_finish_kernel, dim3(static_cast<unsigned>(m)), dim3(NB_THREADS), 0, s, block, m, ni,
+                         d_ids + b, inv);
     });
   });
 }

@@ -12,6 +12,10 @@ bit for bit, float64 - and factor models (iALS, truncated SVD, NMF, BPR with its
 float32 through the MFMA tiles.  A model whose
 class overrides ``get_score_block`` scores some other way and is not recognised (``TypeError``).
 
+``similar_items`` / ``similar_users`` rank the neighbours of items or users inside the resident operand
+(``irs_serve_neighbors``): rows of ``W`` (or of the user-kNN ``U``) for similarity models, cosine or dot product of
+the embedding tables for factor models.  Nothing in the reference corresponds to them.
+
 The operands are copied when the ``DeviceRecommender`` is made: a model that is trained further needs a new one
 (``irspack_amd.utils.IDMapper`` keeps one per model and notices).
 """
@@ -192,6 +196,54 @@ def _exclusions(seen: sps.csr_matrix, forbidden: Optional[Sequence[Sequence[int]
     return np.ascontiguousarray(indptr, dtype=np.int64), np.ascontiguousarray(indices, dtype=np.int32)
 
 
+def embedding_width(model: Any) -> int:
+    """How many leading columns of a factor model's tables are the embedding (``k_used`` of
+    ``irs_serve_neighbors``).  Host only; ``TypeError`` for a class without factor tables.
+
+    BPR and WARP: ``n_components`` - the bias column of ``[V | b]`` and the 1 of ``[U | 1]`` do not count.
+    Mult-VAE: the table width minus 2, the decoder's hidden width (``W4`` for items, ``h2`` for users; not ``b4``
+    and 1, nor 1 and ``-lse``).  iALS, truncated SVD and NMF: the whole table, ``k``."""
+    from .recommenders.bpr import BPRFMRecommender
+    from .recommenders.ials import IALSRecommender
+    from .recommenders.multvae import MultVAERecommender
+    from .recommenders.nmf import NMFRecommender
+    from .recommenders.truncsvd import TruncatedSVDRecommender
+
+    if isinstance(model, MultVAERecommender):
+        hidden = model.dec_hidden_dims if model.dec_hidden_dims is not None else model.enc_hidden_dims
+        return int(hidden)
+    if isinstance(model, (BPRFMRecommender, IALSRecommender)):
+        return int(model.n_components)
+    if isinstance(model, TruncatedSVDRecommender):
+        components = getattr(getattr(model, "decomposer_", None), "components_", None)
+        return int(components.shape[0] if components is not None else model.n_components)
+    if isinstance(model, NMFRecommender):
+        H = getattr(model, "H", None)
+        return int(H.shape[0] if isinstance(H, np.ndarray) else model.n_components)
+    raise TypeError(f"{type(model).__name__} has no embedding tables.")
+
+
+_METRICS = {"weight": _lib.NEIGHBOR_WEIGHT, "cosine": _lib.NEIGHBOR_COSINE, "dot": _lib.NEIGHBOR_DOT}
+
+
+class _Handle:
+    """an ``irs_server`` that is destroyed with its last holder (a call keeps the one it runs on)"""
+
+    def __init__(self) -> None:
+        self.h = C.c_void_p()
+
+    def close(self) -> None:
+        h, self.h = self.h, C.c_void_p()
+        if h.value:
+            lib().irs_serve_destroy(h)
+
+    def __del__(self) -> None:
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def arrays_to_lists(idx: np.ndarray, score: np.ndarray, length: np.ndarray) -> List[List[Tuple[int, float]]]:
     return [[(int(i), float(s)) for i, s in zip(idx[r, :length[r]], score[r, :length[r]])]
             for r in range(idx.shape[0])]
@@ -209,6 +261,17 @@ class DeviceRecommender:
     ``[0, n_items)`` dropped.  ``forbidden`` is one list of indices per row.  Best first, no item whose score is
     ``-inf``, equal scores in candidate order (also on the host path that a profile row with a repeated column
     takes: a stable sort of the candidates).
+
+    ``similar_items_arrays(item_indices, cutoff, ...)`` and ``similar_users_arrays(user_indices, cutoff, ...)``
+    (``similar_items`` / ``similar_users`` for lists) rank the neighbours of each query entity among all items /
+    users, the entity itself never among them; the lists are shaped like the recommend pair's, ``allowed`` /
+    ``per_item_allowed`` / ``forbidden`` hold item indices on the item side and user indices on the user side.
+    ``metric``: ``"weight"`` for similarity kinds (the stored weights of the row of ``W``, or of ``U`` for user-kNN;
+    an entity without a stored weight in a sparse row is never listed), ``"cosine"`` (the default) or ``"dot"`` for
+    factor kinds, over the embedding columns only (``embedding_width``).  The item side of a user-similarity model
+    and the user side of an item-similarity model do not exist (``NotImplementedError``).  The user side has a
+    device copy of its own (the user table, or ``U``), made at the first ``similar_users`` call: a snapshot like
+    the item side's, dropped by ``drop_user_side()``.
 
     The model is needed at every call (its training rows, its new-user embedding).  ``weak_model=True`` keeps only
     a weak reference to it, for a holder whose entry must die with the model (``IDMapper``'s per-model cache): a
@@ -235,6 +298,9 @@ class DeviceRecommender:
         # (models without get_score_cold_user, as in the reference: user-kNN and BPR)
         self._cold_users = self.kind != "user_similarity" and \
             getattr(type(model), "get_score_cold_user", None) is not BaseRecommender.get_score_cold_user
+        self._k_used = embedding_width(model) if self.kind in ("factors", "ials") else 0
+        self._user_side: Optional[_Handle] = None
+        self.user_side_key: Any = None  # (for a holder that watches the user-side operand: IDMapper)
         dev = C.c_int32(self.device)
         if self.kind in ("similarity", "user_similarity"):
             profiles, W = operands
@@ -273,6 +339,12 @@ class DeviceRecommender:
         h, self._h = getattr(self, "_h", None), C.c_void_p()
         if h is not None and h.value:
             lib().irs_serve_destroy(h)
+        self.drop_user_side()
+
+    def drop_user_side(self) -> None:
+        """lets go of the user-side device copy (the next ``similar_users`` call makes a new one); a call that
+        still runs on it on another thread keeps it until it returns"""
+        self._user_side = None
 
     def __del__(self) -> None:
         try:
@@ -421,3 +493,105 @@ class DeviceRecommender:
                            per_user_allowed: Optional[Sequence[Sequence[int]]] = None,
                            forbidden: Optional[Sequence[Sequence[int]]] = None) -> List[List[Tuple[int, float]]]:
         return arrays_to_lists(*self.recommend_profiles_arrays(X, cutoff, allowed, per_user_allowed, forbidden))
+
+    # ---- neighbours -----------------------------------------------------------------------------------------
+    def user_side_arrays(self) -> List[np.ndarray]:
+        """the host arrays the user-side device copy is a snapshot of (the user table; ``U`` of a user-kNN model)"""
+        if self._users is not None:
+            return [self._users]
+        if self.kind == "user_similarity":
+            return [self._profiles.indptr, self._profiles.indices, self._profiles.data]
+        raise NotImplementedError(f"{self._model_name} has no user side to find neighbours in.")
+
+    def _user_handle(self) -> _Handle:
+        held = self._user_side
+        if held is not None:
+            return held
+        held, dev = _Handle(), C.c_int32(self.device)
+        if self._users is not None:
+            users = self._users
+            check(lib().irs_serve_create_factors(C.c_int64(users.shape[0]), C.c_int32(users.shape[1]),
+                                                 ptr(users, C.c_float), dev, C.byref(held.h)))
+        else:
+            U = _canonical_rows(self._profiles)
+            indptr = np.ascontiguousarray(U.indptr, dtype=np.int64)
+            indices = np.ascontiguousarray(U.indices, dtype=np.int32)
+            data = np.ascontiguousarray(U.data, dtype=np.float64)
+            check(lib().irs_serve_create_similarity(
+                C.c_int64(U.shape[0]), C.c_int64(U.shape[1]), ptr(indptr, C.c_int64), ptr(indices, C.c_int32),
+                ptr(data, C.c_double), dev, C.byref(held.h)))
+        self._user_side = held
+        return held
+
+    def _metric_code(self, metric: Optional[str]) -> int:
+        factor = self.kind in ("factors", "ials")
+        if metric is None:
+            metric = "cosine" if factor else "weight"
+        if metric not in _METRICS:
+            raise ValueError(f"metric must be one of {sorted(_METRICS)}, not {metric!r}.")
+        if factor != (metric != "weight"):
+            raise ValueError(f"metric {metric!r} does not fit a {self.kind} model: "
+                             + ("'cosine' or 'dot'." if factor else "'weight'."))
+        return _METRICS[metric]
+
+    def _neighbors(self, h: C.c_void_p, n: int, what: str, indices: Any, cutoff: int,
+                   allowed: Optional[Sequence[int]], per_row_allowed: Optional[Sequence[Sequence[int]]],
+                   forbidden: Optional[Sequence[Sequence[int]]], metric: int) -> ArrayTriple:
+        cutoff = self._check_cutoff(cutoff)
+        ids = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
+        if ids.size and (ids.min() < 0 or ids.max() >= n):
+            raise IndexError(f"{what} index out of range.")
+        rows = int(ids.size)
+        if per_row_allowed is not None:
+            if len(per_row_allowed) != rows:
+                raise ValueError(f"per_{what}_allowed must hold one list per row.")
+            lists = list(per_row_allowed)
+        else:
+            lists = [allowed] if allowed is not None else []
+        excl = _exclusions(sps.csr_matrix((rows, n), dtype=np.float64), forbidden, n)
+        width = max(min(cutoff, n), 0)
+        idx, score = np.full((rows, width), -1, dtype=np.int32), np.zeros((rows, width), dtype=np.float32)
+        length = np.zeros(rows, dtype=np.int32)
+        if rows == 0:
+            return idx, score, length
+        lptr, litems = _ragged(lists)
+        check(lib().irs_serve_neighbors(
+            h, C.c_int64(rows), ptr(ids, C.c_int64), C.c_int32(metric), C.c_int32(self._k_used),
+            ptr(excl[0], C.c_int64), ptr(excl[1], C.c_int32), C.c_int64(len(lists)), ptr(lptr, C.c_int64),
+            ptr(litems, C.c_int64), C.c_int64(cutoff), ptr(idx, C.c_int32), ptr(score, C.c_float),
+            ptr(length, C.c_int32)))
+        return idx, score, length
+
+    def similar_items_arrays(self, item_indices: Any, cutoff: int, allowed: Optional[Sequence[int]] = None,
+                             per_item_allowed: Optional[Sequence[Sequence[int]]] = None,
+                             forbidden: Optional[Sequence[Sequence[int]]] = None,
+                             metric: Optional[str] = None) -> ArrayTriple:
+        if self.kind == "user_similarity":
+            raise NotImplementedError(f"{self._model_name} has no item side to find neighbours in.")
+        return self._neighbors(self._h, self.n_items, "item", item_indices, cutoff, allowed, per_item_allowed,
+                               forbidden, self._metric_code(metric))
+
+    def similar_users_arrays(self, user_indices: Any, cutoff: int, allowed: Optional[Sequence[int]] = None,
+                             per_user_allowed: Optional[Sequence[Sequence[int]]] = None,
+                             forbidden: Optional[Sequence[Sequence[int]]] = None,
+                             metric: Optional[str] = None) -> ArrayTriple:
+        if self.kind in ("similarity", "dense_similarity"):
+            raise NotImplementedError(f"{self._model_name} has no user side to find neighbours in.")
+        code = self._metric_code(metric)
+        held = self._user_handle()  # (kept for the length of the call)
+        return self._neighbors(held.h, self.n_users, "user", user_indices, cutoff, allowed, per_user_allowed,
+                               forbidden, code)
+
+    def similar_items(self, item_indices: Any, cutoff: int, allowed: Optional[Sequence[int]] = None,
+                      per_item_allowed: Optional[Sequence[Sequence[int]]] = None,
+                      forbidden: Optional[Sequence[Sequence[int]]] = None,
+                      metric: Optional[str] = None) -> List[List[Tuple[int, float]]]:
+        return arrays_to_lists(*self.similar_items_arrays(item_indices, cutoff, allowed, per_item_allowed, forbidden,
+                                                          metric))
+
+    def similar_users(self, user_indices: Any, cutoff: int, allowed: Optional[Sequence[int]] = None,
+                      per_user_allowed: Optional[Sequence[Sequence[int]]] = None,
+                      forbidden: Optional[Sequence[Sequence[int]]] = None,
+                      metric: Optional[str] = None) -> List[List[Tuple[int, float]]]:
+        return arrays_to_lists(*self.similar_users_arrays(user_indices, cutoff, allowed, per_user_allowed, forbidden,
+                                                          metric))

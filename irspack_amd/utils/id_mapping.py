@@ -7,6 +7,10 @@ top-k stay on the device.  Any other model, and a batch below the model kind's `
 reference's two steps - ``get_score_remove_seen`` / ``get_score_cold_user_remove_seen`` on the host, then
 ``retrieve_recommend_from_score`` (which orders equal scores inside an unsorted allowed list by item index; the
 device path keeps them in the order of the list).
+
+``ItemIDMapper.similar_items`` / ``similar_items_batch`` and ``IDMapper.similar_users`` / ``similar_users_batch``
+have no counterpart in the reference: the neighbours of items or users by ID, ranked inside the model's resident
+operand (``DeviceRecommender.similar_items`` / ``similar_users``), always on the device.
 """
 
 import ctypes as C
@@ -112,6 +116,28 @@ def _device_recommender(recommender: Any, n_rows: int, new_users: bool = False) 
         closer.atexit = False  # (at interpreter exit the handle goes with the process)
         _recommenders[recommender] = _Held(key, served, closer)
         return served
+
+
+def _neighbour_recommender(recommender: Any, n_rows: int, user_side: bool = False) -> Any:
+    """The model's cached ``DeviceRecommender`` for a neighbour call, whatever the batch size: these calls have no
+    host path, so a model the device does not recognise raises ``DeviceRecommender``'s ``TypeError``.  The user
+    side has a device copy of its own, made at its first use; the operand it was made from (the user table, or the
+    ``U`` of a user-kNN model) is read in place by every other call and so is no part of the per-call key:
+    its fingerprint is taken here, and the copy is let go of when it differs from the one taken when the copy was
+    made."""
+    from .. import serving
+
+    found = serving.model_operands(recommender)
+    if found is None:
+        return serving.DeviceRecommender(recommender)  # (raises)
+    dev = _device_recommender(recommender, max(n_rows, DEVICE_MIN_BATCH.get(found[0], 0), 1))
+    if user_side and found[0] not in ("similarity", "dense_similarity"):
+        key = tuple(_fingerprint(a) for a in dev.user_side_arrays())
+        with _cache_lock:
+            if dev.user_side_key != key:
+                dev.drop_user_side()
+                dev.user_side_key = key
+    return dev
 
 
 class ItemIDMapper(Generic[ItemIdType]):
@@ -235,6 +261,45 @@ class ItemIDMapper(Generic[ItemIdType]):
             score, cutoff, allowed_item_ids=allowed_item_ids, per_user_allowed_item_ids=per_user_allowed_item_ids,
             forbidden_item_ids=forbidden_item_ids, n_threads=get_n_threads(n_threads=n_threads))
 
+    def similar_items(
+        self,
+        recommender: "BaseRecommender",
+        item_id: ItemIdType,
+        cutoff: int = 20,
+        allowed_item_ids: Optional[List[ItemIdType]] = None,
+        forbidden_item_ids: Optional[List[ItemIdType]] = None,
+        metric: Optional[str] = None,
+    ) -> List[Tuple[ItemIdType, float]]:
+        """``(item_id, score)`` pairs, best first, of the items most like ``item_id`` in the model - never the item
+        itself (no counterpart in the reference; ``DeviceRecommender.similar_items``).  Always on the device.  An
+        ID that is not in ``self.item_ids`` raises ``RuntimeError``; unknown IDs inside the lists are dropped."""
+        return self.similar_items_batch(
+            recommender, [item_id], cutoff=cutoff, allowed_item_ids=allowed_item_ids,
+            forbidden_item_ids=None if forbidden_item_ids is None else [forbidden_item_ids], metric=metric)[0]
+
+    def similar_items_batch(
+        self,
+        recommender: "BaseRecommender",
+        item_ids: List[ItemIdType],
+        cutoff: int = 20,
+        allowed_item_ids: Optional[List[ItemIdType]] = None,
+        per_item_allowed_item_ids: Optional[List[List[ItemIdType]]] = None,
+        forbidden_item_ids: Optional[List[List[ItemIdType]]] = None,
+        metric: Optional[str] = None,
+    ) -> List[List[Tuple[ItemIdType, float]]]:
+        """One best-first list of ``(item_id, score)`` per query item ID.  ``per_item_allowed_item_ids`` wins over
+        ``allowed_item_ids``; ``metric`` as in ``DeviceRecommender.similar_items``."""
+        self._require_n_items(recommender)
+        for iid in item_ids:
+            if iid not in self.item_id_to_index:
+                raise RuntimeError(f"Item with item_id {iid} not found.")
+        rows = np.asarray([self.item_id_to_index[iid] for iid in item_ids], dtype=np.int64)
+        dev = _neighbour_recommender(recommender, rows.size)
+        allowed, per_item, forbidden = self._batch_lists_as_indices(
+            rows.size, allowed_item_ids, per_item_allowed_item_ids, forbidden_item_ids)
+        return self._arrays_to_id_lists(
+            *dev.similar_items_arrays(rows, cutoff, allowed, per_item, forbidden, metric))
+
     def score_to_recommended_items(
         self,
         score: np.ndarray,
@@ -348,3 +413,58 @@ class IDMapper(Generic[UserIdType, ItemIdType], ItemIDMapper[ItemIdType]):
             score, cutoff=cutoff, allowed_item_ids=allowed_item_ids,
             per_user_allowed_item_ids=per_user_allowed_item_ids, forbidden_item_ids=forbidden_item_ids,
             n_threads=get_n_threads(n_threads=n_threads))
+
+    def _known_user_indices(self, ids: Iterable[UserIdType]) -> List[int]:
+        """indices of the user IDs this mapper knows, in the order given; unknown IDs are dropped"""
+        lookup = self.user_id_to_index
+        return [lookup[uid] for uid in ids if uid in lookup]
+
+    def similar_users(
+        self,
+        recommender: "BaseRecommender",
+        user_id: UserIdType,
+        cutoff: int = 20,
+        allowed_user_ids: Optional[List[UserIdType]] = None,
+        forbidden_user_ids: Optional[List[UserIdType]] = None,
+        metric: Optional[str] = None,
+    ) -> List[Tuple[UserIdType, float]]:
+        """``(user_id, score)`` pairs, best first, of the users most like ``user_id`` in the model - never the user
+        itself (no counterpart in the reference; ``DeviceRecommender.similar_users``).  Always on the device.  An
+        ID that is not in ``self.user_ids`` raises ``RuntimeError``; unknown IDs inside the lists are dropped."""
+        return self.similar_users_batch(
+            recommender, [user_id], cutoff=cutoff, allowed_user_ids=allowed_user_ids,
+            forbidden_user_ids=None if forbidden_user_ids is None else [forbidden_user_ids], metric=metric)[0]
+
+    def similar_users_batch(
+        self,
+        recommender: "BaseRecommender",
+        user_ids: List[UserIdType],
+        cutoff: int = 20,
+        allowed_user_ids: Optional[List[UserIdType]] = None,
+        per_user_allowed_user_ids: Optional[List[List[UserIdType]]] = None,
+        forbidden_user_ids: Optional[List[List[UserIdType]]] = None,
+        metric: Optional[str] = None,
+    ) -> List[List[Tuple[UserIdType, float]]]:
+        """One best-first list of ``(user_id, score)`` per query user ID.  ``per_user_allowed_user_ids`` wins over
+        ``allowed_user_ids``.  The device copy of the user-side operand is remade when that operand was edited in
+        place since the copy was made."""
+        self._require_n_users(recommender)
+        for uid in user_ids:
+            if uid not in self.user_id_to_index:
+                raise RuntimeError(f"User with user_id {uid} not found.")
+        rows = np.asarray([self.user_id_to_index[uid] for uid in user_ids], dtype=np.int64)
+        if forbidden_user_ids is not None:
+            assert len(forbidden_user_ids) == rows.size
+        if per_user_allowed_user_ids is not None:
+            assert len(per_user_allowed_user_ids) == rows.size
+        allowed = per_user = forbidden = None
+        if per_user_allowed_user_ids is not None:
+            per_user = [self._known_user_indices(ids) for ids in per_user_allowed_user_ids]
+        elif allowed_user_ids is not None:
+            allowed = self._known_user_indices(allowed_user_ids)
+        if forbidden_user_ids is not None:
+            forbidden = [self._known_user_indices(ids) for ids in forbidden_user_ids]
+        dev = _neighbour_recommender(recommender, rows.size, user_side=True)
+        idx, score, length = dev.similar_users_arrays(rows, cutoff, allowed, per_user, forbidden, metric)
+        return [[(self.user_ids[int(u)], float(s)) for u, s in zip(idx[r, :length[r]], score[r, :length[r]])]
+                for r in range(idx.shape[0])]
